@@ -1,15 +1,20 @@
 #!/usr/bin/env python3
 """Benchmark of the two hot paths on MI355X (contract: one JSON line on rank 0).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up the C3 scene, warms up, times K steps and prints the line (metric, value, unit,
+ms_per_step, config). --full adds every other leg to the same line: the counting pass and roofline, the
+wavefront tracer, viewer protocol, GPU BVH builders, 3DGS (C2, 1M, 10M), hybrid, C1, torus, capture, C5 and
+the CPU baselines. --dump-outputs DIR writes the accumulator the last timed step left as DIR/radiance.npy.
 
 Primary metric (BASELINE.json): Mrays/s of the path tracer on C3 — the 250k-triangle Sponza-like
 atrium at 1920x1080, 64 samples per pixel per GPU (one step = one 64-spp frame = one launch of
 pt_camera_kernel). Rays = extension + shadow segments, counted exactly by the kernel.
 Multi-GPU: sample-index shard (rank g renders frame counts g, g+N, ...; weak scaling: 64 spp per
 GPU) + one RCCL reduce (sum) of the radiance buffer to rank 0 inside the timed region.
-Secondary (same JSON line, "gs"): 3DGS forward on C2 — 100k Gaussians at 1920x1080, Gsplats/s.
+Secondary (same JSON line, "gs", with --full): 3DGS forward on C2 — 100k Gaussians at 1920x1080, Gsplats/s.
 """
 from __future__ import annotations
 
@@ -64,7 +69,36 @@ def parse():
                          "sample shard + RCCL all-reduce, splat-over composite by tile-row shard + reduce; "
                          "~20 s of scene generation and two ~4 s frames on one GPU)")
     ap.add_argument("--c5", action="store_true", help="(default; kept for old command lines)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline leg also run every other leg (roofline counting pass, wavefront, viewer, "
+                         "GPU BVH builders, 3DGS, hybrid, C1, torus, capture, C5, CPU baselines); the --no-* options "
+                         "and --headline-only choose among those legs. Without it only the C3 path trace is set up, "
+                         "warmed up and timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the headline leg's last timed step left in the caller's "
+                         "buffer as DIR/<name>.npy (float32; rank 0): radiance.npy, the C3 accumulator (H, W, 4); "
+                         "with --full --no-pt splat_image.npy, the C2 frame. An array over the size limit is written "
+                         "as a fixed, seeded sample of its rows with the row indices beside it")
+    args = ap.parse_args()
+    if args.no_pt and not args.full:
+        ap.error("--no-pt chooses among the legs of --full (a plain run times the C3 path trace only)")
+    return args
+
+
+DUMP_LIMIT_BYTES = 48_000_000  # per array; a run writes one array (the headline leg's)
+
+
+def dump_output(dirname: str, name: str, tensor) -> None:
+    """Write one output of the timed path as dirname/name.npy (float32). An array over DUMP_LIMIT_BYTES is
+    reduced to a seeded choice of its rows (the same rows every run), their indices in name_rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    a = np.ascontiguousarray(tensor.detach().cpu().numpy(), dtype=np.float32)
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        keep = max(1, int(DUMP_LIMIT_BYTES // max(1, a.nbytes // a.shape[0])))
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+        np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+        a = a[rows]
+    np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def _profiled(kernel: str, need_traffic: bool = True):
@@ -233,6 +267,7 @@ def main():
     from pathtracer_gaussiansplatting_amd import synthetic as Y
 
     W, H, SPP = args.width, args.height, args.spp
+    full = args.full  # (a plain run: the C3 path trace's set-up, warm-up and timed steps alone)
     r = Renderer(dev)
     stream = torch.cuda.current_stream()
     from pathtracer_gaussiansplatting_amd import dist as D
@@ -286,6 +321,21 @@ def main():
         dt_max = max_over_ranks(dt)
         rays_total = sum_over_ranks(rays_local)
         mrays = rays_total / dt_max / 1e6
+        if args.dump_outputs and rank == 0:
+            dump_output(args.dump_outputs, "radiance", accum)  # (before any later leg renders into it)
+        out.update({
+            "value": round(mrays, 3), "unit": "Mrays/s", "ms_per_step": round(dt_max / args.steps * 1e3, 3),
+            "data": "synthetic: seeded procedural 250k-triangle atrium (no dataset/network)",
+            "config": {"workload": f"C3 path trace: {args.triangles}-tri Sponza-like atrium, {W}x{H}, {SPP} spp per GPU",
+                       "width": W, "height": H, "spp_per_gpu": SPP, "triangles": int(info.num_triangles),
+                       "bvh_nodes": int(info.num_bvh_nodes), "bvh_depth": int(info.bvh_depth),
+                       "bvh_build": f"host binned SAH, {info.build_ms:.1f} ms",
+                       "parallelism": "single GPU" if world == 1 else f"sample-shard x{world} + RCCL reduce"},
+            "rays_per_step": rays_total / args.steps,
+            "samples_per_s": st.samples * world / dt_max,
+            "kernel_ms": round(kernel_ms, 3),
+        })
+    if not args.no_pt and full:
         # instrumented counting pass (same scene / camera, count_spp samples) -> bytes per ray
         r.set_flags(FLAG_COUNT_TRAVERSAL)
         r.stats_reset(stream)
@@ -310,16 +360,6 @@ def main():
         prof = _profiled("pt_camera_kernel")
         traffic = prof["hbm_bytes_per_launch"] if prof else None
         out.update({
-            "value": round(mrays, 3), "unit": "Mrays/s", "ms_per_step": round(dt_max / args.steps * 1e3, 3),
-            "data": "synthetic: seeded procedural 250k-triangle atrium (no dataset/network)",
-            "config": {"workload": f"C3 path trace: {args.triangles}-tri Sponza-like atrium, {W}x{H}, {SPP} spp per GPU",
-                       "width": W, "height": H, "spp_per_gpu": SPP, "triangles": int(info.num_triangles),
-                       "bvh_nodes": int(info.num_bvh_nodes), "bvh_depth": int(info.bvh_depth),
-                       "bvh_build": f"host binned SAH, {info.build_ms:.1f} ms",
-                       "parallelism": "single GPU" if world == 1 else f"sample-shard x{world} + RCCL reduce"},
-            "rays_per_step": rays_total / args.steps,
-            "samples_per_s": st.samples * world / dt_max,
-            "kernel_ms": round(kernel_ms, 3),
             "roofline": _roofline("pt_camera_kernel", traffic, kernel_ms, prof, {
                 "bound": "l2", "achieved": round(achieved, 2), "peak": L2_PEAK_GBS, "unit": "GB/s",
                 "frac": round(achieved / L2_PEAK_GBS, 5), "alg_bytes_per_launch": alg_bytes,
@@ -402,7 +442,7 @@ def main():
         del accum
 
     # ------------------------------------------------------------------ 3DGS (C2)
-    if not args.no_gs:
+    if full and not args.no_gs:
         g = Y.gaussians_c2(args.gaussians, seed=1)  # one scene: every rank holds all Gaussians
         dg0 = {k: torch.from_numpy(v).cuda() for k, v in g.items()}  # the generator's (random) order
         # scene preparation (untimed, like the BVH build): a copy in 3D Morton order of the means with
@@ -497,6 +537,8 @@ def main():
         barrier()
         gdt = max_over_ranks(time.perf_counter() - t0)
         c2_spilled = assert_complete(r, "C2 timed loop")
+        if args.no_pt and args.dump_outputs and rank == 0:
+            dump_output(args.dump_outputs, "splat_image", img)  # (the headline leg here; before later legs reuse img)
 
         def frame_latency_ms():  # one frame from its call to its image, alone (median of 21)
             lat = []
@@ -802,7 +844,7 @@ def main():
     # ------------------------------------------------------------------ hybrid (C4), one GPU
     # C2-distributed Gaussians (seed 3) placed in the C3 camera's frame + the C3 mesh: path trace
     # (hybrid_spp), primary-hit depth, splat over the traced frame (build-defined).
-    if not args.no_pt and not args.no_hybrid and world == 1:
+    if full and not args.no_pt and not args.no_hybrid and world == 1:
         hg = Y.gaussians_in_view(args.hybrid_gaussians, 3, make_ubo(pose, scene, 0, height=H))
         hdg = {k: torch.from_numpy(v).cuda() for k, v in hg.items()}
         haccum = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda")
@@ -841,7 +883,7 @@ def main():
 
     # ------------------------------------------------------------------ C1: Cornell box, 256x256, 1 spp
     # (BASELINE config 1, the reference's CPU-runnable case: here on the GPU, one launch per frame)
-    if not args.no_pt and not args.no_c1 and world == 1:
+    if full and not args.no_pt and not args.no_c1 and world == 1:
         from pathtracer_gaussiansplatting_amd import cornell_box_scene
         c1 = cornell_box_scene()
         c1.blue_noise = Y.blue_noise(1024)
@@ -868,7 +910,7 @@ def main():
     # ------------------------------------------------------------------ torus data collection
     # rt_datacollect: 1M RaySamples (the reference's RANDOM generator, Morton-sorted) shot from the
     # torus around the C1 Cornell box, 16 accumulation frames into the HitData running mean
-    if not args.no_pt and not args.no_torus and world == 1:
+    if full and not args.no_pt and not args.no_torus and world == 1:
         from pathtracer_gaussiansplatting_amd import HITDATA_DTYPE, cornell_box_scene, torus_push
         tsc = cornell_box_scene()
         tsc.blue_noise = Y.blue_noise(1024)
@@ -899,7 +941,7 @@ def main():
     # Engine::captureSceneData: views on the toroidal pose sequence, each accumulated on the GPU, sRGB8,
     # every-2nd-pixel downscale, JPEG q90, transforms_{train,test}.json, then the torus point cloud
     # (1M RaySamples) -> points3d.ply; 8 of the reference's 336 positions, 128 of its 512 steps
-    if not args.no_pt and not args.no_capture and world == 1:
+    if full and not args.no_pt and not args.no_capture and world == 1:
         import shutil
         import tempfile
         from pathtracer_gaussiansplatting_amd import HITDATA_DTYPE, capture, cornell_box_scene, torus_push
@@ -936,7 +978,7 @@ def main():
     # ranks' tile rows (each receives the sums under its own splat rows), mean + primary-hit depth,
     # splat-over of its tile rows, row gather to rank 0 (dist.render_hybrid_frame; SURVEY 8e: strong
     # scaling).
-    if not args.no_c5 and not args.no_pt:
+    if full and not args.no_c5 and not args.no_pt:
         from pathtracer_gaussiansplatting_amd import ACCUM_SUM as _SUM
         from pathtracer_gaussiansplatting_amd import dist as D
         W5, H5, T5, G5, SPP5 = 3840, 2160, 1_000_000, 10_000_000, 256
@@ -1001,7 +1043,7 @@ def main():
         del dg5, acc5, dep5, comp5
 
     # ------------------------------------------------------------------ CPU baseline (rank 0, N=1)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_pt:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_pt:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle
         oracle.build()

@@ -39,7 +39,7 @@ def main():
     js = [l for l in bench.splitlines() if l.startswith("{")]
     if js:
         d = json.loads(js[-1])
-        d["_provenance"] = f"builder gpurun ({tag}): python bench.py --gpus 1 --steps 20 --warmup 5, source tree {rev}"
+        d["_provenance"] = f"builder run ({tag}): python bench.py --full --gpus 1 --steps 20 --warmup 5, source tree {rev}"
         json.dump(d, open(os.path.join(ROOT, "profiles", f"{tag}_bench.json"), "w"), indent=1)
     print("\n".join(lines[:8]))
 
