@@ -55,7 +55,13 @@ extern "C" {
 #define PTGS_EBADIDS (-7) /* an EARLIER stream-ordered splat frame of this context met ptgs_gaussians.ids
                            * entries >= count (those Gaussians were dropped). Returned once, like
                            * PTGS_EINCOMPLETE, by a call that has rendered its own frame; a code of its
-                           * own so a caller can tell it from this call's PTGS_EINVAL. */
+                           * own so a caller can tell it from this call's PTGS_EINVAL.
+                           * Order of the reports: a call returns one code. When earlier frames left both
+                           * reports (one frame may: ids >= count and an exhausted pool), the first call
+                           * after them returns PTGS_EBADIDS, the call after that PTGS_EINCOMPLETE, the
+                           * third PTGS_OK; each of the two has rendered its own frame completely. A
+                           * call that fails for a reason of its own (PTGS_EINVAL, PTGS_EHIP) returns
+                           * that code and leaves the reports to the calls after it. */
 
 /* ---------------- reference struct layouts (Appendix B of SURVEY.md) ---------------- */
 
@@ -444,7 +450,11 @@ typedef struct ptgs_trace_stats {
                                       * so inputs (Gaussians, ids, chunk bounds) written on the stream during a
                                       * run must be followed by one call without this flag — like a Vulkan frame
                                       * in flight, whose resources the application does not touch. Same image,
-                                      * keys and counts as without the flag. */
+                                      * keys and counts as without the flag. A call rejected with PTGS_EINVAL
+                                      * (with or without the flag) enqueues nothing and is no part of a run: it
+                                      * neither ends one nor takes a workspace, and ptgs_splat_get_buffers /
+                                      * ptgs_splat_get_tile_rows / ptgs_splat_status_read go on describing the
+                                      * latest rendered frame. */
 int ptgs_set_flags(ptgs_ctx* ctx, uint32_t flags);
 int ptgs_stats_reset(ptgs_ctx* ctx, void* hip_stream);
 int ptgs_stats_read(ptgs_ctx* ctx, ptgs_trace_stats* out); /* synchronises the context's device */

@@ -704,14 +704,11 @@ int ptgs_synchronize(ptgs_ctx* c) {
 
 extern "C" {
 
-// Renders one frame; PTGS_OK means it was enqueued completely. *report (bit 0: an earlier frame was left
-// incomplete, bit 1: an earlier frame met ids >= count) is about EARLIER frames of the workspace: the
-// caller turns it into PTGS_EINCOMPLETE / PTGS_EINVAL (splat_report) once everything it renders is enqueued.
-static int splat_render(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t w, uint32_t h,
-                        const float bg[3], const float* depth, const float* under, uint32_t tile_row_begin,
-                        uint32_t tile_row_end, float* out, ptgs_splat_stats* stats, void* stream, uint32_t* report,
-                        const SplatOverlap* ov = nullptr, SplatSeq* seq = nullptr) {
-  *report = 0;
+// The argument checks of a splat frame that need no device work. Every entry point runs them before it
+// changes any state of the context (the overlap ring above all: a rejected call must leave `splat`, the
+// ring position and the run's blend ordinals as the latest rendered frame left them).
+static int splat_check_args(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t w, uint32_t h,
+                            const float* depth, const float* under, const float* out) {
   if (w == 0 || h == 0 || w > 32768 || h > 32768) return fail(c, PTGS_EINVAL, "bad image size %ux%u", w, h);
   if (g->count && (!is_device_ptr(g->means) || !is_device_ptr(g->scales) || !is_device_ptr(g->rotations) ||
                    !is_device_ptr(g->opacities) || !is_device_ptr(g->colors) || (g->ids && !is_device_ptr(g->ids))))
@@ -720,6 +717,18 @@ static int splat_render(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ub
   if ((depth && !is_device_ptr(depth)) || (under && !is_device_ptr(under)))
     return fail(c, PTGS_EINVAL, "depth / under must be device pointers");
   if (ubo->proj[0] == 0.0f || ubo->proj[5] == 0.0f) return fail(c, PTGS_EINVAL, "degenerate projection");
+  return PTGS_OK;
+}
+
+// Renders one frame whose arguments passed splat_check_args; PTGS_OK means it was enqueued completely.
+// *report (bit 0: an earlier frame was left incomplete, bit 1: an earlier frame met ids >= count) is about
+// EARLIER frames of the workspace: the caller turns it into PTGS_EINCOMPLETE / PTGS_EBADIDS (splat_report)
+// once everything it renders is enqueued.
+static int splat_render(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t w, uint32_t h,
+                        const float bg[3], const float* depth, const float* under, uint32_t tile_row_begin,
+                        uint32_t tile_row_end, float* out, ptgs_splat_stats* stats, void* stream, uint32_t* report,
+                        const SplatOverlap* ov = nullptr, SplatSeq* seq = nullptr) {
+  *report = 0;
   HIPCHK(c, hipSetDevice(c->device));
   float mvp[16];
   mat4_mul(ubo->proj, ubo->view, mvp);
@@ -733,9 +742,10 @@ static int splat_render(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ub
 
 // (the frames of this call are rendered; the codes report earlier frames of the workspace(s))
 static int splat_report(ptgs_ctx* c, uint32_t report);
-// The reports a call collected (earlier frames' flags, consumed from the workspaces) and its own result:
-// a failing call keeps them for the next call (they are returned once, never dropped); a
-// successful one returns them together with any kept earlier.
+// The reports a call collected (earlier frames' flags, consumed from the workspaces) and its own result.
+// Each kind of report is returned once, never dropped, one per call: a failing call keeps them all for
+// the next call; a successful one returns one of them (with any kept earlier: bad ids first)
+// and keeps the other for the call after it (splat_report; the order is ptgs.h's, PTGS_EBADIDS).
 static int splat_finish(ptgs_ctx* c, int rc, uint32_t report) {
   report |= c->pending_report;
   c->pending_report = 0;
@@ -746,7 +756,10 @@ static int splat_finish(ptgs_ctx* c, int rc, uint32_t report) {
   return splat_report(c, report);
 }
 static int splat_report(ptgs_ctx* c, uint32_t report) {
-  if (report & 2u) return fail(c, PTGS_EBADIDS, "an earlier splat frame met ptgs_gaussians.ids entries >= count");
+  if (report & 2u) {
+    c->pending_report = report & 1u;  // (an incomplete frame too: the next call's PTGS_EINCOMPLETE)
+    return fail(c, PTGS_EBADIDS, "an earlier splat frame met ptgs_gaussians.ids entries >= count");
+  }
   if (report & 1u)
     return fail(c, PTGS_EINCOMPLETE, "an earlier splat frame left tiles incomplete (spill pool exhausted; grown)");
   return PTGS_OK;
@@ -853,6 +866,12 @@ static int splat_common(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ub
   SplatOverlap ov{};
   SplatSeq seq{};
   const SplatOverlap* ovp = nullptr;
+  // (before the ring advances: after a rejected call ptgs_splat_get_buffers / _get_tile_rows / _status_read
+  // still describe the latest rendered frame, and the run goes on as if the call had not been made: no
+  // entry of ov_ord / ov_strm is written and ov_started is not advanced, so the next front end's wait
+  // value is still the ordinal of a blend that splat_overlap_end recorded as launched, or the marker)
+  const int bad = splat_check_args(c, g, ubo, w, h, depth, under, out);
+  if (bad != PTGS_OK) return bad;
   if (c->flags & PTGS_FLAG_SPLAT_OVERLAP) {
     const int rc = splat_overlap_begin(c, (hipStream_t)stream, &ov, &seq);
     if (rc != PTGS_OK) return rc;
@@ -888,6 +907,10 @@ int ptgs_splat_gaussians_views(ptgs_ctx* c, const ptgs_gaussians* g, uint32_t n_
   for (uint32_t v = 0; v < n_views; ++v)
     if (!outs[v]) return fail(c, PTGS_EINVAL, "null output of view %u", v);
   if (n_views == 1) return splat_common(c, g, &ubos[0], w, h, bg, nullptr, nullptr, 0, ~0u, outs[0], nullptr, stream);
+  for (uint32_t v = 0; v < n_views; ++v) {  // (every view's arguments before any view is forked)
+    const int bad = splat_check_args(c, g, &ubos[v], w, h, nullptr, nullptr, outs[v]);
+    if (bad != PTGS_OK) return bad;
+  }
   HIPCHK(c, hipSetDevice(c->device));
   c->ov_started = 0;  // (view 0 renders serially on the caller's stream with the latest workspace)
   const hipStream_t s = (hipStream_t)stream;

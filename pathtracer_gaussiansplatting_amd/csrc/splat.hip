@@ -1106,6 +1106,8 @@ template <> struct GsFusedShape<256> {
   static constexpr uint32_t slice = 2048u;
   static constexpr uint32_t lds_cap = 2048u;  // 8 KB (+ 5.6 KB static): within one blend workgroup's LDS
 };
+static_assert(GsFusedShape<256>::lds_cap == 2048u,
+              "tests/test_splat_windows_gpu.py picks its frame sizes around this window (WINDOW): change both");
 
 // The count walk of one slice [p0, p1) of a chunk's pairs (at most GS_FUSED_QREG per work-item): the
 // chunk's rects (s_e: x0 | w << 16, y0 | h << 16, key index, depth bits) and the inclusive scan of
