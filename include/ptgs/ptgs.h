@@ -34,7 +34,9 @@ extern "C" {
 #endif
 
 #define PTGS_ABI_VERSION 4  /* 3: ptgs_gaussians.ids, ptgs_splat_stats.fused, ptgs_splat_status spill fields;
-                             * 4: PTGS_EBADIDS, PTGS_FLAG_SPLAT_OVERLAP */
+                             * 4: PTGS_EBADIDS, PTGS_FLAG_SPLAT_OVERLAP. Added since, without a version
+                             * change (new functions only): ptgs_gaussians_sh_colors, ptgs_gaussians_activate,
+                             * ptgs_gaussians_permute_sh; ptgs_read_gaussian_ply in ptgs_host.h */
 
 /* ---------------- error codes ---------------- */
 #define PTGS_OK 0
@@ -558,6 +560,52 @@ int ptgs_gaussians_sort_spatial(ptgs_ctx* ctx, const ptgs_gaussians* g, float* m
  * ptgs_gaussians.chunk_bounds; useful when chunks are spatially compact (ptgs_gaussians_sort_spatial's
  * order). Recompute after the Gaussians change. Stream-ordered. */
 int ptgs_gaussians_chunk_bounds(ptgs_ctx* ctx, const ptgs_gaussians* g, float* bounds, void* hip_stream);
+
+/* Trained 3DGS checkpoints (the point_cloud.ply of Kerbl et al. 2023; ptgs_read_gaussian_ply in
+ * ptgs_host.h reads one): view-dependent colour from spherical harmonics, the activations, and the SH
+ * rows of a reordered copy. All pointers are device pointers; the calls are stream-ordered, do not
+ * synchronise the host and allocate nothing. PTGS_EINVAL: a null context, a degree above 3,
+ * active_degree > sh_degree, a null pointer. count == 0 (checked before the array pointers: empty
+ * arrays may be null): PTGS_OK, nothing is launched.
+ *
+ * ptgs_gaussians_sh_colors: colors[3 i..] = max(SH(dir_i) + 0.5, 0) for ptgs_gaussians.colors; call it
+ * on the frame's stream before ptgs_splat_gaussians (with PTGS_FLAG_SPLAT_OVERLAP colors is then an
+ * input written during a run: see that flag).
+ * sh: float[count][(sh_degree+1)^2][3] (coefficient-major, rgb innermost: the trainers' `features`
+ * tensor). sh_degree in 0..3 is the STORED degree (row stride); active_degree <= sh_degree is how many
+ * bands are evaluated. camera_pos is read by the host during the call.
+ * Numerical contract (f32, no FMA, no reassociation: checkable bit for bit like the splat):
+ *   d = means[i] - camera_pos; len = sqrt((d.x*d.x + d.y*d.y) + d.z*d.z);
+ *   (x, y, z) = len > 0 ? d / len : (0, 0, 0)      (a Gaussian at the eye gets its DC colour, not NaN)
+ *   per channel, computeColorFromSH of the original rasterizer's forward.cu evaluated left to right
+ *   as written there (a*b*s = (a*b)*s, a*b*(e)*s = ((a*b)*(e))*s, sums term by term in index order):
+ *   res = C0*sh[0]
+ *   degree >= 1: res = res - C1*y*sh[1] + C1*z*sh[2] - C1*x*sh[3]
+ *   degree >= 2: res = res + C2[0]*xy*sh[4] + C2[1]*yz*sh[5] + C2[2]*(2*zz - xx - yy)*sh[6]
+ *                          + C2[3]*xz*sh[7] + C2[4]*(xx - yy)*sh[8]
+ *   degree >= 3: res = res + C3[0]*y*(3*xx - yy)*sh[9] + C3[1]*xy*z*sh[10] + C3[2]*y*(4*zz - xx - yy)*sh[11]
+ *                          + C3[3]*z*(2*zz - 3*xx - 3*yy)*sh[12] + C3[4]*x*(4*zz - xx - yy)*sh[13]
+ *                          + C3[5]*z*(xx - yy)*sh[14] + C3[6]*x*(3*xx - yy)*sh[15]
+ *   color = res + 0.5 < 0 ? 0 : res + 0.5
+ *   C0 = 0.28209479177387814, C1 = 0.4886025119029199,
+ *   C2 = {1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792,
+ *         0.5462742152960396},
+ *   C3 = {-0.5900435899266435, 2.890611442640554, -0.4570457994644658, 0.3731763325901154,
+ *         -0.4570457994644658, 1.445305721320277, -0.5900435899266435}, each rounded to f32. */
+int ptgs_gaussians_sh_colors(ptgs_ctx* ctx, const float* means, const float* sh, uint32_t count,
+                             uint32_t sh_degree, uint32_t active_degree, const float camera_pos[3],
+                             float* colors, void* hip_stream);
+/* scales = exp(log_scales) (3N), opacities = 1 / (1 + exp(-logits)) (N); in place allowed (scales ==
+ * log_scales, opacities == opacity_logits). exp is the renderer's deterministic polynomial (detmath.h
+ * expx: exp2 of x * 1.44269504088896341 by a degree-6 polynomial), the opacity 1.0f / (1.0f + expx(-o)).
+ * Rotations need no activation: ptgs_gaussians.rotations are un-normalised. */
+int ptgs_gaussians_activate(ptgs_ctx* ctx, const float* log_scales, const float* opacity_logits,
+                            uint32_t count, float* scales, float* opacities, void* hip_stream);
+/* out[i] = sh[ids[i]] (rows of (sh_degree+1)^2 * 3 floats): SH rows for a copy made by
+ * ptgs_gaussians_sort_spatial. out must not alias sh. A row whose id is >= count is written as zeros
+ * (never read out of bounds). */
+int ptgs_gaussians_permute_sh(ptgs_ctx* ctx, const float* sh, uint32_t sh_degree, const uint32_t* ids,
+                              uint32_t count, float* out, void* hip_stream);
 
 /* Report of the stream-ordered splat (no stats): waits for hip_stream and the context's view streams,
  * then returns (and clears) the counts since the last query. frames / views[v]: frames left

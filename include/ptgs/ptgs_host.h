@@ -166,6 +166,20 @@ typedef struct ptgs_scene_settings {
 int ptgs_builder_load_scene_json(ptgs_scene_builder* b, const char* path, const char* root_dir, uint32_t flags,
                                  ptgs_scene_settings* settings);
 
+/* Trained-3DGS checkpoint (the point_cloud.ply of Kerbl et al. 2023). Vertex element: x y z,
+ * f_dc_0..2, f_rest_0..(3((d+1)^2-1)-1), opacity, scale_0..2, rot_0..3 (w x y z), matched by name in
+ * any order (other properties, e.g. nx ny nz, are skipped); ascii / binary LE / BE like ptgs_read_ply.
+ * The degree d follows from the number of f_rest_* properties (0, 9, 24, 45 -> 0, 1, 2, 3).
+ * Host outputs, each may be NULL: means 3N, log_scales 3N, rotations 4N, opacity_logits N, sh
+ * N * (d+1)^2 * 3 in the layout of ptgs_gaussians_sh_colors ([i][k][c]: sh[i][0][c] = f_dc_c,
+ * sh[i][k][c] = f_rest[c * ((d+1)^2 - 1) + (k - 1)]: the file is channel-major). Values are the
+ * file's, not activated (ptgs_gaussians_activate). All outputs NULL: returns count and sh_degree only.
+ * PTGS_EIO: unreadable / malformed file, another f_rest_* count, a gap in the numbering, a missing
+ * property; PTGS_ERANGE: capacity < count. */
+int ptgs_read_gaussian_ply(const char* path, float* means, float* log_scales, float* rotations,
+                           float* opacity_logits, float* sh, uint32_t capacity,
+                           uint32_t* count, uint32_t* sh_degree);
+
 #ifdef __cplusplus
 }
 #endif

@@ -209,6 +209,9 @@ SYMBOLS = {
     "ptgs_splat_reserve": (_I, [_P, _U]),
     "ptgs_gaussians_sort_spatial": (_I, [_P, C.POINTER(Gaussians), _P, _P, _P, _P, _P, _P, _P]),
     "ptgs_gaussians_chunk_bounds": (_I, [_P, C.POINTER(Gaussians), _P, _P]),
+    "ptgs_gaussians_sh_colors": (_I, [_P, _P, _P, _U, _U, _U, _FP, _P, _P]),
+    "ptgs_gaussians_activate": (_I, [_P, _P, _P, _U, _P, _P, _P]),
+    "ptgs_gaussians_permute_sh": (_I, [_P, _P, _U, _P, _U, _P, _P]),
     "ptgs_trace_depth_rows": (_I, [_P, C.POINTER(Ubo), _U, _U, _U, _U, _P, _P]),
     "ptgs_knn3_mean_dist2": (_I, [_P, _P, _U, _P, _P]),
     "ptgs_gaussians_from_points": (_I, [_P, _P, _P, _U, _P, _P, _P, _P, _P, _P]),
@@ -246,6 +249,7 @@ SYMBOLS = {
     "ptgs_builder_last_error": (C.c_char_p, [_P]),
     "ptgs_image_decode_rgba8": (_I, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(_U), C.POINTER(_U), C.POINTER(_U)]),
     "ptgs_read_ply": (_I, [C.c_char_p, _P, _P, _P, _U, C.POINTER(_U)]),
+    "ptgs_read_gaussian_ply": (_I, [C.c_char_p, _P, _P, _P, _P, _P, _U, C.POINTER(_U), C.POINTER(_U)]),
     "ptgs_generate_samples": (_I, [_I, _U, _P, _U, _P, _U, _U, _I, _P]),
     "ptgs_sort_samples": (_I, [_P, _U]),
     "ptgs_morton2d": (_U, [C.c_float, C.c_float]),

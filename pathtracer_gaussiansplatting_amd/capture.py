@@ -71,6 +71,27 @@ def read_ply(path: str, lib=None):
     return xyz, nrm, rgb
 
 
+def load_gaussian_ply(path: str, lib=None) -> dict:
+    """A trained-3DGS checkpoint (point_cloud.ply) -> dict of numpy float32 arrays as the file stores
+    them (not activated: Renderer.activate_gaussians): means (N, 3), log_scales (N, 3), rotations (N, 4;
+    w x y z), opacity_logits (N,), sh (N, (d+1)^2, 3) in the layout of Renderer.sh_colors, and sh_degree
+    d (int). Raises PtgsError (code PTGS_EIO) for a file that is not such a checkpoint."""
+    L = _lib(lib)
+    n, d = C.c_uint32(), C.c_uint32()
+    rc = L.ptgs_read_gaussian_ply(path.encode(), None, None, None, None, None, 0, C.byref(n), C.byref(d))
+    _abi.check(rc, "ptgs_read_gaussian_ply", f"({path})")
+    N, K = n.value, (d.value + 1) ** 2
+    g = {"means": np.zeros((N, 3), np.float32), "log_scales": np.zeros((N, 3), np.float32),
+         "rotations": np.zeros((N, 4), np.float32), "opacity_logits": np.zeros((N,), np.float32),
+         "sh": np.zeros((N, K, 3), np.float32)}
+    rc = L.ptgs_read_gaussian_ply(path.encode(), g["means"].ctypes.data, g["log_scales"].ctypes.data,
+                                  g["rotations"].ctypes.data, g["opacity_logits"].ctypes.data, g["sh"].ctypes.data,
+                                  N, C.byref(n), C.byref(d))
+    _abi.check(rc, "ptgs_read_gaussian_ply", f"({path})")
+    g["sh_degree"] = int(d.value)
+    return g
+
+
 def write_jpeg(path: str, pixels: np.ndarray, quality: int = 90, lib=None):
     p = np.ascontiguousarray(pixels, np.uint8)
     comp = 1 if p.ndim == 2 else p.shape[2]

@@ -32,6 +32,7 @@
 #include "pt_wavefront.h"
 #include "comm.h"
 #include "splat.h"
+#include "splat_sh.h"
 #include "textures.h"
 
 using namespace ptgs;
@@ -985,6 +986,52 @@ int ptgs_gaussians_chunk_bounds(ptgs_ctx* c, const ptgs_gaussians* g, float* bou
   HIPCHK(c, hipSetDevice(c->device));
   const hipError_t e = splat_chunk_bounds(g, bounds, (hipStream_t)stream);
   if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_chunk_bounds: %s", hipGetErrorString(e));
+  return PTGS_OK;
+}
+
+int ptgs_gaussians_sh_colors(ptgs_ctx* c, const float* means, const float* sh, uint32_t count, uint32_t sh_degree,
+                             uint32_t active_degree, const float camera_pos[3], float* colors, void* stream) {
+  if (!c) return PTGS_EINVAL;
+  if (sh_degree > 3) return fail(c, PTGS_EINVAL, "sh_degree %u above 3", sh_degree);
+  if (active_degree > sh_degree)
+    return fail(c, PTGS_EINVAL, "active_degree %u above the stored sh_degree %u", active_degree, sh_degree);
+  if (count == 0) return PTGS_OK;  // (empty arrays may be null)
+  if (!means || !sh || !camera_pos || !colors) return fail(c, PTGS_EINVAL, "null argument");
+  // (a per-frame call: one pointer query, of the array that is written, like the other frame entry points)
+  if (!is_device_ptr(colors)) return fail(c, PTGS_EINVAL, "colors is not a device pointer");
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipError_t e =
+      splat_sh_colors(means, sh, count, sh_degree, active_degree, camera_pos, colors, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_sh_colors: %s", hipGetErrorString(e));
+  return PTGS_OK;
+}
+
+int ptgs_gaussians_activate(ptgs_ctx* c, const float* log_scales, const float* opacity_logits, uint32_t count,
+                            float* scales, float* opacities, void* stream) {
+  if (!c) return PTGS_EINVAL;
+  if (count == 0) return PTGS_OK;
+  if (!log_scales || !opacity_logits || !scales || !opacities) return fail(c, PTGS_EINVAL, "null argument");
+  if (!is_device_ptr(log_scales) || !is_device_ptr(opacity_logits) || !is_device_ptr(scales) ||
+      !is_device_ptr(opacities))
+    return fail(c, PTGS_EINVAL, "log_scales / opacity_logits / scales / opacities must be device pointers");
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipError_t e = splat_sh_activate(log_scales, opacity_logits, count, scales, opacities, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_activate: %s", hipGetErrorString(e));
+  return PTGS_OK;
+}
+
+int ptgs_gaussians_permute_sh(ptgs_ctx* c, const float* sh, uint32_t sh_degree, const uint32_t* ids, uint32_t count,
+                              float* out, void* stream) {
+  if (!c) return PTGS_EINVAL;
+  if (sh_degree > 3) return fail(c, PTGS_EINVAL, "sh_degree %u above 3", sh_degree);
+  if (count == 0) return PTGS_OK;
+  if (!sh || !ids || !out) return fail(c, PTGS_EINVAL, "null argument");
+  if (out == sh) return fail(c, PTGS_EINVAL, "out must not alias sh");
+  if (!is_device_ptr(sh) || !is_device_ptr(ids) || !is_device_ptr(out))
+    return fail(c, PTGS_EINVAL, "sh / ids / out must be device pointers");
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipError_t e = splat_sh_permute(sh, sh_degree, ids, count, out, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_permute_sh: %s", hipGetErrorString(e));
   return PTGS_OK;
 }
 

@@ -1,0 +1,19 @@
+// splat_sh.h — per-frame colours of trained 3DGS checkpoints (see splat_sh.hip).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace ptgs {
+
+// colors[3 i..] = max(SH(dir_i) + 0.5, 0); sh rows of (sh_degree + 1)^2 * 3 floats, active_degree <= sh_degree <= 3
+hipError_t splat_sh_colors(const float* means, const float* sh, uint32_t count, uint32_t sh_degree,
+                           uint32_t active_degree, const float cam[3], float* colors, hipStream_t s);
+// scales = expx(log_scales) (3N), opacities = 1 / (1 + expx(-logits)) (N)
+hipError_t splat_sh_activate(const float* log_scales, const float* logits, uint32_t count, float* scales,
+                             float* opacities, hipStream_t s);
+// out row i = sh row ids[i] (a row of zeros for ids[i] >= count)
+hipError_t splat_sh_permute(const float* sh, uint32_t sh_degree, const uint32_t* ids, uint32_t count, float* out,
+                            hipStream_t s);
+
+}  // namespace ptgs

@@ -1,0 +1,217 @@
+// splat_sh.hip — what a trained 3DGS checkpoint (Kerbl et al. 2023, point_cloud.ply) needs before the
+// rasterizer of splat.hip can draw it: view-dependent colours from spherical-harmonic coefficients,
+// the activations of the stored scales / opacities, and the SH rows of a reordered copy. The
+// rasterizer itself is untouched: it keeps reading ptgs_gaussians.colors, which gs_sh_colors_kernel
+// writes on the frame's stream before the splat call.
+//
+// Colour (computeColorFromSH of the original rasterizer's forward.cu, per channel c, f32, no FMA,
+// evaluated left to right as written; sh[k] = the k-th coefficient of the Gaussian's row):
+//   d = mean - camera_pos; len = sqrt((d.x*d.x + d.y*d.y) + d.z*d.z); (x, y, z) = len > 0 ? d / len : 0
+//   res = C0 * sh[0]
+//   degree >= 1:  res = res - C1*y*sh[1] + C1*z*sh[2] - C1*x*sh[3]
+//   degree >= 2:  xx = x*x, yy = y*y, zz = z*z, xy = x*y, yz = y*z, xz = x*z
+//                 res = res + C2[0]*xy*sh[4] + C2[1]*yz*sh[5] + C2[2]*(2*zz - xx - yy)*sh[6]
+//                           + C2[3]*xz*sh[7] + C2[4]*(xx - yy)*sh[8]
+//   degree >= 3:  res = res + C3[0]*y*(3*xx - yy)*sh[9] + C3[1]*xy*z*sh[10] + C3[2]*y*(4*zz - xx - yy)*sh[11]
+//                           + C3[3]*z*(2*zz - 3*xx - 3*yy)*sh[12] + C3[4]*x*(4*zz - xx - yy)*sh[13]
+//                           + C3[5]*z*(xx - yy)*sh[14] + C3[6]*x*(3*xx - yy)*sh[15]
+//   color = fmaxx(res + 0.5, 0)
+// A product a*b*s is (a*b)*s, a*b*(e)*s is ((a*b)*(e))*s, and a sum adds its terms one by one in index
+// order, so the factor in front of sh[k] depends on the direction only and is computed once for the
+// three channels.
+//
+// Memory: the kernel is a stream (12 B mean + 12 K B coefficients in, 12 B out per Gaussian, K =
+// (degree + 1)^2). A degree-3 row is 192 B: work-items that each walk their own row give every load
+// instruction 64 rows to touch. So a workgroup of 256 work-items loads the contiguous block of its 256
+// rows with lane-contiguous loads (16 B per lane; 4 B per lane when the base is not 16-B aligned),
+// stages it in LDS and each work-item reads its coefficients from there. The LDS row stride is the row
+// length made odd (13 / 27 / 49 dwords): 32 lanes reading coefficient j of 32 consecutive rows then
+// hit 32 different banks. Degree 0 has one coefficient per channel and reads it directly.
+// -DPTGS_SH_ROWWISE builds the row-per-work-item form (no staging) for the A/B of DESIGN.md.
+#include "splat_sh.h"
+
+#include "detmath.h"
+
+namespace ptgs {
+namespace {
+
+constexpr int SH_WG = 256;  // Gaussians per workgroup (the chunk granule of splat.hip)
+constexpr int SH_BATCH = 4;  // staging loads in flight per work-item
+
+constexpr float SH_C0 = 0.28209479177387814f;
+constexpr float SH_C1 = 0.4886025119029199f;
+__device__ constexpr float SH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
+                                       -1.0925484305920792f, 0.5462742152960396f};
+__device__ constexpr float SH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f,
+                                       0.3731763325901154f,  -0.4570457994644658f, 1.445305721320277f,
+                                       -0.5900435899266435f};
+
+constexpr int sh_row(int deg) { return 3 * (deg + 1) * (deg + 1); }
+
+// row: the Gaussian's coefficients [k][c]; active <= DEG bands are evaluated
+template <int DEG>
+__device__ __forceinline__ void sh_eval(const float* row, uint32_t active, v3 dir, float* out) {
+  float res[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) res[c] = SH_C0 * row[c];
+  if (DEG >= 1 && active >= 1) {
+    const float x = dir.x, y = dir.y, z = dir.z;
+    const float w1 = SH_C1 * y, w2 = SH_C1 * z, w3 = SH_C1 * x;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) res[c] = res[c] - w1 * row[3 + c] + w2 * row[6 + c] - w3 * row[9 + c];
+    if (DEG >= 2 && active >= 2) {
+      const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+      const float w4 = SH_C2[0] * xy, w5 = SH_C2[1] * yz, w6 = SH_C2[2] * (2.0f * zz - xx - yy);
+      const float w7 = SH_C2[3] * xz, w8 = SH_C2[4] * (xx - yy);
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        res[c] = res[c] + w4 * row[12 + c] + w5 * row[15 + c] + w6 * row[18 + c] + w7 * row[21 + c] +
+                 w8 * row[24 + c];
+      if (DEG >= 3 && active >= 3) {
+        const float w9 = SH_C3[0] * y * (3.0f * xx - yy), w10 = SH_C3[1] * xy * z;
+        const float w11 = SH_C3[2] * y * (4.0f * zz - xx - yy);
+        const float w12 = SH_C3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy);
+        const float w13 = SH_C3[4] * x * (4.0f * zz - xx - yy), w14 = SH_C3[5] * z * (xx - yy);
+        const float w15 = SH_C3[6] * x * (3.0f * xx - yy);
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          res[c] = res[c] + w9 * row[27 + c] + w10 * row[30 + c] + w11 * row[33 + c] + w12 * row[36 + c] +
+                   w13 * row[39 + c] + w14 * row[42 + c] + w15 * row[45 + c];
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out[c] = fmaxx(res[c] + 0.5f, 0.0f);
+}
+
+// One workgroup: Gaussians [256 b, 256 b + 256) ∩ [0, count). VEC: sh is 16-B aligned (a block starts
+// 256 rows = a multiple of 16 B after it), so the block is loaded as float4 plus a dword tail.
+template <int DEG, bool VEC>
+__global__ __launch_bounds__(SH_WG) void gs_sh_colors_kernel(const float* __restrict__ means,
+                                                            const float* __restrict__ sh, uint32_t count,
+                                                            uint32_t active, v3 cam, float* __restrict__ colors) {
+  constexpr uint32_t R = sh_row(DEG);  // floats per row
+  constexpr uint32_t S = R | 1u;       // LDS row stride
+  const uint32_t first = blockIdx.x * (uint32_t)SH_WG, t = threadIdx.x;
+  const uint32_t left = count - first, nrows = left < (uint32_t)SH_WG ? left : (uint32_t)SH_WG;
+  const float* src = sh + (size_t)first * R;
+#if defined(PTGS_SH_ROWWISE)
+  const float* row = src + (size_t)t * R;
+#else
+  __shared__ float rows[DEG == 0 ? 1 : SH_WG * S];
+  const float* row = DEG == 0 ? src + (size_t)t * R : rows + t * S;
+  if (DEG > 0) {
+    const uint32_t nfl = nrows * R;  // the block's floats: nothing at or past src + nfl is read
+    auto put = [&](uint32_t f, float v) { rows[f + (f / R) * (S - R)] = v; };
+    // SH_BATCH loads per work-item are issued before the first is stored, to keep bytes in flight
+    uint32_t done = 0;
+    if (VEC) {
+      const uint32_t nv = nfl >> 2;
+      for (uint32_t q0 = t; q0 < nv; q0 += SH_BATCH * SH_WG) {
+        float4 v[SH_BATCH];
+#pragma unroll
+        for (int j = 0; j < SH_BATCH; ++j)
+          if (q0 + j * SH_WG < nv) v[j] = reinterpret_cast<const float4*>(src)[q0 + j * SH_WG];
+#pragma unroll
+        for (int j = 0; j < SH_BATCH; ++j) {
+          const uint32_t q = q0 + j * SH_WG;
+          if (q < nv) {
+            put(4 * q, v[j].x);
+            put(4 * q + 1, v[j].y);
+            put(4 * q + 2, v[j].z);
+            put(4 * q + 3, v[j].w);
+          }
+        }
+      }
+      done = nv << 2;  // (at most 3 floats are left)
+    }
+    for (uint32_t f0 = done + t; f0 < nfl; f0 += SH_BATCH * SH_WG) {
+      float v[SH_BATCH];
+#pragma unroll
+      for (int j = 0; j < SH_BATCH; ++j)
+        if (f0 + j * SH_WG < nfl) v[j] = src[f0 + j * SH_WG];
+#pragma unroll
+      for (int j = 0; j < SH_BATCH; ++j)
+        if (f0 + j * SH_WG < nfl) put(f0 + j * SH_WG, v[j]);
+    }
+    __syncthreads();
+  }
+#endif
+  if (t >= nrows) return;
+  const size_t i3 = (size_t)(first + t) * 3;
+  const v3 d = mk3(means[i3], means[i3 + 1], means[i3 + 2]) - cam;
+  const float len = length3(d);
+  const v3 dir = len > 0.0f ? d / len : mk3(0.0f);
+  float rgb[3];
+  sh_eval<DEG>(row, active, dir, rgb);
+  colors[i3] = rgb[0];
+  colors[i3 + 1] = rgb[1];
+  colors[i3 + 2] = rgb[2];
+}
+
+__global__ __launch_bounds__(256) void gs_activate_kernel(const float* log_scales, const float* logits, uint32_t count,
+                                                         float* scales, float* opacities) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < (size_t)count * 3) scales[i] = expx(log_scales[i]);
+  if (i < count) opacities[i] = 1.0f / (1.0f + expx(-logits[i]));
+}
+
+// one work-item per output float: contiguous writes, reads contiguous within a row
+__global__ __launch_bounds__(256) void gs_permute_sh_kernel(const float* __restrict__ sh, uint32_t R,
+                                                           const uint32_t* __restrict__ ids, uint32_t count,
+                                                           float* __restrict__ out) {
+  const size_t f = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (f >= (size_t)count * R) return;
+  const uint32_t i = (uint32_t)(f / R), col = (uint32_t)(f - (size_t)i * R);
+  const uint32_t id = ids[i];
+  out[f] = id < count ? sh[(size_t)id * R + col] : 0.0f;
+}
+
+template <int DEG>
+hipError_t launch_sh(const float* means, const float* sh, uint32_t count, uint32_t active, v3 cam, float* colors,
+                     hipStream_t s) {
+  const uint32_t blocks = (uint32_t)(((uint64_t)count + SH_WG - 1) / SH_WG);
+  if constexpr (DEG > 0) {  // (degree 0 stages nothing)
+    if (((uintptr_t)sh & 15u) == 0) {
+      gs_sh_colors_kernel<DEG, true><<<blocks, SH_WG, 0, s>>>(means, sh, count, active, cam, colors);
+      return hipGetLastError();
+    }
+  }
+  gs_sh_colors_kernel<DEG, false><<<blocks, SH_WG, 0, s>>>(means, sh, count, active, cam, colors);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t splat_sh_colors(const float* means, const float* sh, uint32_t count, uint32_t sh_degree,
+                           uint32_t active_degree, const float cam[3], float* colors, hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  const v3 c = mk3(cam[0], cam[1], cam[2]);
+  switch (sh_degree) {
+    case 0: return launch_sh<0>(means, sh, count, active_degree, c, colors, s);
+    case 1: return launch_sh<1>(means, sh, count, active_degree, c, colors, s);
+    case 2: return launch_sh<2>(means, sh, count, active_degree, c, colors, s);
+    case 3: return launch_sh<3>(means, sh, count, active_degree, c, colors, s);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t splat_sh_activate(const float* log_scales, const float* logits, uint32_t count, float* scales,
+                             float* opacities, hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  const uint32_t blocks = (uint32_t)(((uint64_t)count * 3 + 255) / 256);
+  gs_activate_kernel<<<blocks, 256, 0, s>>>(log_scales, logits, count, scales, opacities);
+  return hipGetLastError();
+}
+
+hipError_t splat_sh_permute(const float* sh, uint32_t sh_degree, const uint32_t* ids, uint32_t count, float* out,
+                            hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  const uint32_t R = (uint32_t)sh_row((int)sh_degree);
+  const uint64_t blocks = ((uint64_t)count * R + 255) / 256;
+  if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  gs_permute_sh_kernel<<<(uint32_t)blocks, 256, 0, s>>>(sh, R, ids, count, out);
+  return hipGetLastError();
+}
+
+}  // namespace ptgs

@@ -296,6 +296,83 @@ class Renderer:
                   "ptgs_gaussians_chunk_bounds")
         return out
 
+    # ---------------------------------------------------------------- trained 3DGS checkpoints
+    @staticmethod
+    def _sh_degree(sh) -> int:
+        k = int(sh.shape[1]) if sh.dim() == 3 else 0
+        if sh.dim() != 3 or int(sh.shape[2]) != 3 or k not in (1, 4, 9, 16):
+            raise _abi.PtgsError(f"sh must be [N, (d+1)^2, 3] with d in 0..3 (got {tuple(sh.shape)})")
+        return (1, 4, 9, 16).index(k)
+
+    @staticmethod
+    def _f32(*named):
+        """Every (name, tensor, elements) is a float32 tensor of exactly that many elements (the kernels
+        index by the count alone)."""
+        import torch
+        for name, t, numel in named:
+            if t.dtype != torch.float32 or t.numel() != numel:
+                raise _abi.PtgsError(f"{name} must be float32 with {numel} elements (got {t.dtype}, {t.numel()})")
+
+    def sh_colors(self, means, sh, camera_pos, out=None, active_degree=None, stream=None):
+        """ptgs_gaussians_sh_colors: linear RGB [N, 3] of SH coefficients sh [N, (d+1)^2, 3] seen from
+        camera_pos (max(SH(dir) + 0.5, 0)); active_degree (default: the stored degree d) bands are
+        evaluated. Stream-ordered; writes `out` (allocated when None) and returns it."""
+        import torch
+        d = self._sh_degree(sh)
+        n = int(means.shape[0])
+        if out is None:
+            out = torch.empty((n, 3), dtype=torch.float32, device=means.device)
+        self._f32(("means", means, n * 3), ("sh", sh, n * (d + 1) ** 2 * 3), ("out", out, n * 3))
+        cam = np.ascontiguousarray(np.asarray(camera_pos, np.float32).reshape(3))
+        rc = self.lib.ptgs_gaussians_sh_colors(self._h, _ptr(means), _ptr(sh), n, d,
+                                               d if active_degree is None else int(active_degree), _abi.fptr(cam),
+                                               _ptr(out), _stream(stream))
+        self._chk(rc, "ptgs_gaussians_sh_colors")
+        return out
+
+    def activate_gaussians(self, log_scales, opacity_logits, stream=None, out=None):
+        """ptgs_gaussians_activate: (scales, opacities) = (exp(log_scales), sigmoid(opacity_logits)) of a
+        checkpoint's stored values, as new tensors; out=(scales, opacities) writes there instead (the
+        inputs themselves: in place)."""
+        import torch
+        n = int(opacity_logits.shape[0])
+        sc, op = out if out is not None else (torch.empty_like(log_scales), torch.empty_like(opacity_logits))
+        self._f32(("log_scales", log_scales, n * 3), ("opacity_logits", opacity_logits, n), ("scales", sc, n * 3),
+                  ("opacities", op, n))
+        rc = self.lib.ptgs_gaussians_activate(self._h, _ptr(log_scales), _ptr(opacity_logits), n, _ptr(sc), _ptr(op),
+                                              _stream(stream))
+        self._chk(rc, "ptgs_gaussians_activate")
+        return sc, op
+
+    def permute_sh(self, sh, ids, stream=None):
+        """ptgs_gaussians_permute_sh: sh[ids] as a new tensor: the SH rows of the copy that
+        sort_gaussians_spatial returned with these ids."""
+        import torch
+        out = torch.empty_like(sh)
+        self._f32(("sh", sh, sh.numel()))
+        if ids.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or ids.numel() != sh.shape[0]:
+            raise _abi.PtgsError(f"ids must be {sh.shape[0]} 32-bit integers")
+        rc = self.lib.ptgs_gaussians_permute_sh(self._h, _ptr(sh), self._sh_degree(sh), _ptr(ids), int(sh.shape[0]),
+                                                _ptr(out), _stream(stream))
+        self._chk(rc, "ptgs_gaussians_permute_sh")
+        return out
+
+    def splat_gaussians_sh(self, g: dict, ubo: Ubo, width: int, height: int, out, active_degree=None, stream=None,
+                           **kwargs):
+        """splat_gaussians of Gaussians whose colour is g["sh"] ([N, (d+1)^2, 3]): sh_colors from
+        ubo.camera_pos into a colors tensor kept for the next call, then splat_gaussians with it on the
+        same stream (other arguments as there). With set_splat_overlap(True) the cached colors are
+        rewritten between overlapped calls: see INTEGRATION.md."""
+        import torch
+        n = int(g["means"].shape[0])
+        col = getattr(self, "_sh_colors", None)
+        if col is None or col.shape[0] != n or col.device != g["means"].device:
+            col = self._sh_colors = torch.empty((n, 3), dtype=torch.float32, device=g["means"].device)
+        self.sh_colors(g["means"], g["sh"], list(ubo.camera_pos), out=col, active_degree=active_degree, stream=stream)
+        gc = {k: v for k, v in g.items() if k != "sh"}
+        gc["colors"] = col
+        return self.splat_gaussians(gc, ubo, width, height, out, stream=stream, **kwargs)
+
     def splat_status(self, stream=None) -> SplatStatus:
         """ptgs_splat_status_read: waits for `stream` and the view streams, returns and clears the
         counts since the last query: frames left incomplete (spill pool exhausted), tiles completed
