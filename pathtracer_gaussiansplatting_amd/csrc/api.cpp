@@ -390,6 +390,7 @@ int ptgs_scene_upload(ptgs_ctx* c, const ptgs_scene_desc* d) {
   // BVH: the host binned-SAH build (default), or with PTGS_FLAG_GPU_BVH the GPU LBVH (bvh_gpu.hip),
   // falling back to the host build when the LBVH is deeper than the traversal stack
   bool built = false;
+  std::vector<float> host_n4;  // the final 4-wide nodes when the host built them (nodes64 below)
   if ((c->flags & PTGS_FLAG_GPU_BVH) && tris.size() >= 16) {
     GpuBvh g;
     float ms = 0.0f;
@@ -484,6 +485,7 @@ int ptgs_scene_upload(ptgs_ctx* c, const ptgs_scene_desc* d) {
     if (!fits) return fail(c, PTGS_ERANGE, "BVH depth %u exceeds the traversal stack", bvh.depth);
     s.deep_stack = need >= PTGS_STACK ? 1 : 0;
     if ((rc = upload(c, (const float4*)n4.data(), n4.size() / 4, &s.nodes))) return rc;
+    host_n4.swap(n4);
     bvh.num_nodes = num4;
     bvh.depth = dep4;
     if ((rc = upload(c, (const float4*)bvh.tris.data(), bvh.tris.size() / 4, &s.tris))) return rc;
@@ -499,6 +501,19 @@ int ptgs_scene_upload(ptgs_ctx* c, const ptgs_scene_desc* d) {
   if (c->info.num_bvh_nodes > bvh_node_limit())
     return fail(c, PTGS_ERANGE, "BVH of %u 4-wide nodes exceeds the traversal's 2 GiB node window (%u nodes)",
                 c->info.num_bvh_nodes, bvh_node_limit());
+  // The megakernel's traversal reads a compact 64-B copy of the final nodes (bvh.h quantize_bvh4; one
+  // conversion for the host SAH, GPU SAH and LBVH trees: a GPU-built tree is read back for it).
+  {
+    const size_t nf = (size_t)c->info.num_bvh_nodes * 32;
+    if (host_n4.size() != nf) {
+      host_n4.resize(nf);
+      HIPCHK(c, hipMemcpy(host_n4.data(), s.nodes, nf * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    std::vector<uint32_t> n64;
+    if (!quantize_bvh4(host_n4.data(), c->info.num_bvh_nodes, n64))
+      return fail(c, PTGS_ERANGE, "BVH node extents beyond the compact nodes' step range (2^-100 .. 2^100)");
+    if ((rc = upload(c, (const uint4*)n64.data(), n64.size() / 4, &s.nodes64))) return rc;
+  }
   // a zero vertex/index count still needs valid (never dereferenced) pointers
   ptgs_vertex dummy_v{};
   uint32_t dummy_i = 0;

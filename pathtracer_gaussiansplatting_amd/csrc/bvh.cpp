@@ -312,4 +312,69 @@ void collapse_bvh4(const std::vector<float>& n2, std::vector<float>& n4, uint32_
   depth4 = dep[0];
 }
 
+bool quantize_bvh4(const float* n4, uint32_t num, std::vector<uint32_t>& out) {
+  out.assign((size_t)num * PTGS_NODE64_DWORDS, 0u);
+  const float kFar = 1e29f;  // the empty slots' 1e30 planes and anything as far: no ray reaches it
+  float scale = 0.0f;
+  for (size_t k = 0; k < (size_t)num * 32; ++k) {
+    if (k % 32 >= 24) continue;
+    const float v = std::fabs(n4[k]);
+    if (v < kFar) scale = std::max(scale, v);
+  }
+  const double m = (double)(scale * 0x1p-21f + 1e-30f);  // margin beyond the canonical plane
+  for (uint32_t i = 0; i < num; ++i) {
+    const float* f = &n4[32 * (size_t)i];
+    uint32_t* o = &out[PTGS_NODE64_DWORDS * (size_t)i];
+    bool real[4];
+    for (int j = 0; j < 4; ++j) {
+      real[j] = true;
+      for (int a = 0; a < 3; ++a) {
+        const float lo = f[(2 * a) * 4 + j], hi = f[(2 * a + 1) * 4 + j];
+        if (!(std::fabs(lo) < kFar && std::fabs(hi) < kFar && lo <= hi)) real[j] = false;
+      }
+    }
+    for (int a = 0; a < 3; ++a) {
+      const float* lo = f + (2 * a) * 4;
+      const float* hi = f + (2 * a + 1) * 4;
+      float lmin = std::numeric_limits<float>::infinity(), hmax = -lmin;
+      for (int j = 0; j < 4; ++j)
+        if (real[j]) { lmin = std::min(lmin, lo[j]); hmax = std::max(hmax, hi[j]); }
+      float org = 0.0f, step = 1.0f;
+      uint32_t wlo = 0xffffffffu, whi = 0u;  // inverted planes unless set below
+      if (lmin <= hmax) {
+        // (one ulp below the rounded difference: at or below the exact lmin - m)
+        org = std::nextafterf((float)((double)lmin - m), -std::numeric_limits<float>::infinity());
+        int e = (int)std::ceil(std::log2(std::max(((double)hmax + m - (double)org) / 255.0, 1e-300)));
+        e = std::max(e, -100);
+        for (;; ++e) {
+          if (e > 100) return false;
+          step = std::ldexp(1.0f, e);
+          bool fits = true;
+          wlo = 0xffffffffu; whi = 0u;
+          for (int j = 0; j < 4 && fits; ++j) {
+            if (!real[j]) continue;
+            const double tl = (double)lo[j] - m, th = (double)hi[j] + m;
+            double ql = std::floor((tl - (double)org) / (double)step);
+            ql = std::min(std::max(ql, 0.0), 255.0);
+            while (ql > 0.0 && (double)std::fmaf((float)ql, step, org) > tl) ql -= 1.0;
+            double qh = std::ceil((th - (double)org) / (double)step);
+            qh = std::min(std::max(qh, 0.0), 256.0);
+            while (qh <= 255.0 && (double)std::fmaf((float)qh, step, org) < th) qh += 1.0;
+            if (qh > 255.0) { fits = false; break; }
+            wlo = (wlo & ~(0xffu << (8 * j))) | ((uint32_t)ql << (8 * j));
+            whi |= (uint32_t)qh << (8 * j);
+          }
+          if (fits) break;
+        }
+      }
+      std::memcpy(&o[a], &org, 4);
+      std::memcpy(&o[3 + a], &step, 4);
+      o[6 + 2 * a] = wlo;
+      o[7 + 2 * a] = whi;
+    }
+    std::memcpy(&o[12], &f[24], 16);
+  }
+  return true;
+}
+
 }  // namespace ptgs

@@ -44,4 +44,19 @@ void build_bvh(const std::vector<BuildTri>& tris, int max_leaf_size, uint32_t ma
 void collapse_bvh4(const std::vector<float>& nodes2, std::vector<float>& nodes4, uint32_t& num_nodes4,
                    uint32_t& max_stack, uint32_t& depth4, int max_children = 4);
 
+// Compact traversal copy of the 4-wide nodes: 64 B per node (16 dwords), derived from the canonical
+// 128-B nodes above (which stay the reference: ptgs_scene_get_bvh, the builders, the oracle).
+//   [0..2]  origin x, y, z (f32)          [3..5]  step x, y, z (f32, a power of two)
+//   [6..11] byte planes lo.x, hi.x, lo.y, hi.y, lo.z, hi.z: byte j = child j's plane q,
+//           decoded as fmaf(q, step, origin)
+//   [12..15] the four child links, as in the 128-B node
+// Every decoded plane lies outside the canonical (padded) plane by at least 2^-21 x the tree's largest
+// finite coordinate, which covers the extra rounding of the kernel's per-node fold.
+// Empty slots, and children whose canonical box no ray can hit (the 1e30 point boxes), get the inverted
+// planes lo = 255, hi = 0; an empty slot keeps its link 0, which the traversal also tests.
+// Returns false when a node's step would leave [2^-100, 2^100] (coordinates no scene of the tracer's
+// tmax = 1e4 has).
+#define PTGS_NODE64_DWORDS 16
+bool quantize_bvh4(const float* nodes4, uint32_t num_nodes, std::vector<uint32_t>& out);
+
 }  // namespace ptgs

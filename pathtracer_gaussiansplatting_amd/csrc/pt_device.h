@@ -25,7 +25,9 @@ namespace ptgs {
 // reference vertices).
 // ---------------------------------------------------------------------------------------------
 struct DevScene {
-  const float4* nodes;            // 4 float4 per interior node (see bvh.h)
+  const float4* nodes;            // 8 float4 per 4-wide node (see bvh.h)
+  const uint4* nodes64;           // the same nodes quantised to 4 uint4 (bvh.h quantize_bvh4): the
+                                  // megakernel's traversal reads these (PTGS_PT_NODE64)
   const float4* tris;             // 3 float4 per triangle: (v0, mesh_bits) (e1, prim_bits) (e2, gid_bits)
   const uint32_t* tri_flags;      // bit0: non-opaque (any-hit shader runs)
   const ptgs_vertex* vertices;
@@ -362,6 +364,77 @@ __device__ __forceinline__ void box4(const Ray& r, const DevScene& sc, int node,
   }
 }
 #endif
+// PTGS_PT_NODE64: the megakernel's traversals fetch the compact 64-B node (bvh.h quantize_bvh4): four
+// 16-B loads per lane instead of seven. Per node and axis the step and origin are folded into the ray's
+// slab constants (one multiply, exact: the step is a power of two; one FMA), per child plane one byte
+// conversion and one FMA: t = fma(q, step * inv, fma(origin, inv, -oinv)). The direction sign picks the
+// near and far byte planes, as PTGS_PT_NEARFAR picks the float planes. The decoded box contains the
+// canonical padded box for every ray, so the visited nodes are a superset and the hits,
+// ray counts and image do not change. Slots 2 and 3 may be empty (link 0: the root, never a child):
+// they hold inverted planes, and the link is tested too so that no rounding can enter them.
+#ifndef PTGS_PT_NODE64
+#define PTGS_PT_NODE64 1
+#endif
+// PTGS_PT_NODE64_PIN: keep o * inv in registers across the walk (the compiler otherwise recomputes the
+// three products at every node: 3 VALU per node step against 3 VGPRs)
+#ifndef PTGS_PT_NODE64_PIN
+#define PTGS_PT_NODE64_PIN 1
+#endif
+template <bool N64>
+__device__ __forceinline__ Ray node64_ray(const Ray& r) {
+  Ray q = r;
+  if (N64 && PTGS_PT_NODE64_PIN) asm volatile("" : "+v"(q.oinv.x), "+v"(q.oinv.y), "+v"(q.oinv.z));
+  return q;
+}
+__device__ __forceinline__ float node64_q(uint32_t w, int j) { return (float)((w >> (8 * j)) & 0xffu); }
+__device__ __forceinline__ void box4_q(const Ray& r, const DevScene& sc, int node, float tcap, Box4& o) {
+  typedef unsigned int u4 __attribute__((ext_vector_type(4)));
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)sc.nodes64, 0, 0x7fffffff, 0x00020000);
+  const uint32_t base = (uint32_t)node << 6;
+  const u4 a = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)base, 0, 0);
+  const u4 b = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(base + 16u), 0, 0);
+  const u4 p = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(base + 32u), 0, 0);
+  u4 ch = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(base + 48u), 0, 0);
+  asm volatile("" : "+v"(ch.x), "+v"(ch.y), "+v"(ch.z), "+v"(ch.w));  // (pinned: box4 above)
+  const float sx = __uint_as_float(a.w) * r.inv.x, sy = __uint_as_float(b.x) * r.inv.y, sz = __uint_as_float(b.y) * r.inv.z;
+  const float cx = __builtin_fmaf(__uint_as_float(a.x), r.inv.x, -r.oinv.x);
+  const float cy = __builtin_fmaf(__uint_as_float(a.y), r.inv.y, -r.oinv.y);
+  const float cz = __builtin_fmaf(__uint_as_float(a.z), r.inv.z, -r.oinv.z);
+#if PTGS_PT_NEARFAR
+  const bool gx = (r.nx & 16u) != 0u, gy = (r.ny & 16u) != 0u, gz = (r.nz & 16u) != 0u;  // inv < 0: hi is near
+#else
+  const bool gx = r.inv.x < 0.0f, gy = r.inv.y < 0.0f, gz = r.inv.z < 0.0f;
+#endif
+  const uint32_t nX = gx ? b.w : b.z, fX = gx ? b.z : b.w;
+  const uint32_t nY = gy ? p.y : p.x, fY = gy ? p.x : p.y;
+  const uint32_t nZ = gz ? p.w : p.z, fZ = gz ? p.z : p.w;
+  const uint32_t CH[4] = {ch.x, ch.y, ch.z, ch.w};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float x0 = __builtin_fmaf(node64_q(nX, j), sx, cx), x1 = __builtin_fmaf(node64_q(fX, j), sx, cx);
+    const float y0 = __builtin_fmaf(node64_q(nY, j), sy, cy), y1 = __builtin_fmaf(node64_q(fY, j), sy, cy);
+    const float z0 = __builtin_fmaf(node64_q(nZ, j), sz, cz), z1 = __builtin_fmaf(node64_q(fZ, j), sz, cz);
+    const float tn = fmaxf(fmaxf(x0, y0), fmaxf(z0, r.tmin));
+#if PTGS_PT_ASM_MIN
+    float tf;
+    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(tf) : "v"(x1), "v"(y1), "v"(z1));
+    asm("v_min_f32 %0, %1, %2" : "=v"(tf) : "v"(tf), "v"(tcap));
+#else
+    const float tf = fminf(fminf(x1, y1), fminf(z1, tcap));
+#endif
+    // (the two compares' lane masks combined on the scalar unit)
+    unsigned long long hm = __builtin_amdgcn_ballot_w64(tn <= tf * 1.0000004f);
+    if (j >= 2) hm &= __builtin_amdgcn_ballot_w64(CH[j] != 0u);
+    o.tn[j] = __builtin_amdgcn_inverse_ballot_w64(hm) ? tn : __builtin_huge_valf();
+    o.c[j] = (int)CH[j];
+    o.hm[j] = hm;
+  }
+}
+template <bool N64>
+__device__ __forceinline__ void box4_sel(const Ray& r, const DevScene& sc, int node, float tcap, Box4& o) {
+  if (N64) box4_q(r, sc, node, tcap, o);
+  else box4(r, sc, node, tcap, o);
+}
 __device__ __forceinline__ void cswap4(Box4& b, int i, int j) {
   const bool sw = b.tn[j] < b.tn[i];
   const float ti = b.tn[i], tj = b.tn[j];
@@ -386,10 +459,12 @@ __device__ __forceinline__ int enter_box4(Box4& b, Push push, Pop pop) {
 
 // SS: the LDS stack's stride (work-items sharing it); OVF: overflow entries beyond the LDS part (0 for
 // a tree whose stack need fits PTGS_STACK: the overflow's branches and scratch cost 3.4% on C3)
-template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF>
+// N64: fetch the compact nodes (box4_q)
+template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF, bool N64 = false>
 __device__ __forceinline__ Hit trace_closest(const DevScene& sc, const Ray& r, uint32_t seed, int* stack,
                                              TraversalCounters& cnt) {
   Hit h; h.t = r.tmax; h.u = 0.f; h.v = 0.f; h.gid = 0xffffffffu; h.slot = 0;
+  const Ray rq = node64_ray<N64>(r);
   int sp = 0;
   int node = 0;
   // while-while with postponed leaves (Aila & Laine 2009): a lane that reaches a leaf parks it and
@@ -415,7 +490,7 @@ __device__ __forceinline__ Hit trace_closest(const DevScene& sc, const Ray& r, u
     while (node >= 0 && node != DONE) {
       PT_LANE_TICK(cnt, PT_L_NODE);
       Box4 b;
-      box4(r, sc, node, h.t, b);
+      box4_sel<N64>(rq, sc, node, h.t, b);
       if (STATS) cnt.nodes += 4;
       node = enter_box4(b, push, pop);
       if (node < 0 && leaf == DONE) {
@@ -440,9 +515,10 @@ __device__ __forceinline__ Hit trace_closest(const DevScene& sc, const Ray& r, u
   }
 }
 
-template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF>  // (as trace_closest)
+template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF, bool N64 = false>  // (as trace_closest)
 __device__ __forceinline__ bool trace_any(const DevScene& sc, const Ray& r, uint32_t seed, int* stack,
                                           TraversalCounters& cnt) {
+  const Ray rq = node64_ray<N64>(r);
   int sp = 0;
   int node = 0;
   int ovf[OVF > 0 ? OVF : 1];  // entries beyond the LDS part (private: scratch)
@@ -454,7 +530,7 @@ __device__ __forceinline__ bool trace_any(const DevScene& sc, const Ray& r, uint
     while (node >= 0) {
       PT_LANE_TICK(cnt, PT_L_ANY_NODE);
       Box4 b;
-      box4(r, sc, node, r.tmax, b);
+      box4_sel<N64>(rq, sc, node, r.tmax, b);
       if (STATS) cnt.nodes += 4;
       // order is irrelevant for an any-hit query: enter the first hit child, push the others (the
       // closest-hit near-to-far order measured -9% for the shadow rays)
@@ -679,13 +755,13 @@ __device__ __forceinline__ void shadow_towards(ShadowQuery& q, v3 o, v3 light_po
   q.tmax = dist - 0.005f;
 }
 
-template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF>  // (as trace_closest)
+template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF, bool N64 = false>  // (as trace_closest)
 __device__ __forceinline__ void resolve_shadow(ShadeCtx& c, v3& color, uint32_t seed, const ShadowQuery& q,
                                                TraversalCounters& cnt) {
   if (!(q.flags & SQ_TRACE)) return;
   c.shadow_rays++;
   const Ray r = make_ray(q.o, q.d, 0.001f, q.tmax);
-  float vis = trace_any<STATS, TEX, SS, OVF>(*c.sc, r, seed, c.stack, cnt) ? 0.0f : 1.0f;
+  float vis = trace_any<STATS, TEX, SS, OVF, N64>(*c.sc, r, seed, c.stack, cnt) ? 0.0f : 1.0f;
   vis = fmaxx(vis, q.trans);
   if (vis > 0.0f && (q.flags & SQ_VALID)) {
     v3 contrib = (q.pre * vis) * q.post;

@@ -182,13 +182,13 @@ __global__ __launch_bounds__(PTGS_PT_WG, PTGS_PT_MIN_WAVES) void pt_camera_kerne
         p.depth = depth;
         Ray ray = make_ray(ro, rd, 0.001f, 10000.0f);
         ext_rays++;
-        Hit h = trace_closest<STATS, TEX, PTGS_PT_WG, DEEP ? PTGS_STACK_OVF : 0>(sc, ray, p.seed, c.stack, tc);
+        Hit h = trace_closest<STATS, TEX, PTGS_PT_WG, DEEP ? PTGS_STACK_OVF : 0, PTGS_PT_NODE64 != 0>(sc, ray, p.seed, c.stack, tc);
         if (STATS && h.gid != 0xffffffffu) tc.hits++;
         ShadowQuery q;
         q.flags = 0;
         if (h.gid == 0xffffffffu) miss<false>(cp, p);
         else closest_hit<false, TEX>(c, p, ray, h, q);
-        resolve_shadow<STATS, TEX, PTGS_PT_WG, DEEP ? PTGS_STACK_OVF : 0>(c, p.color, p.seed, q, tc);  // NEE visibility after shading
+        resolve_shadow<STATS, TEX, PTGS_PT_WG, DEEP ? PTGS_STACK_OVF : 0, PTGS_PT_NODE64 != 0>(c, p.color, p.seed, q, tc);  // NEE visibility after shading
         acc = acc + p.color * thr;
         acc = vmin(acc, 5.0f);
         if (p.hit_flag < 0.0f) break;

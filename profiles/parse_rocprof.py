@@ -12,6 +12,10 @@ L2 hit rate = TCC_HIT_sum / (TCC_HIT_sum + TCC_MISS_sum).
 VALU lane utilisation = SQ_THREAD_CYCLES_VALU / (64 * SQ_ACTIVE_INST_VALU) (active lanes per issued
 VALU cycle); VALU issue share = SQ_ACTIVE_INST_VALU / SQ_ACTIVE_INST_ANY; wave wait share =
 SQ_WAIT_ANY / SQ_WAVE_CYCLES.
+Vector-memory path (passes 6-8, the TA / TCP / SQ-VMEM counters): TA busy cycles (TA_BUSY_avr, mean over the TAs),
+TA cycles stalled by the L1 (TA_ADDR_STALLED_BY_TC_CYCLES_sum), buffer / flat read wavefronts, L1 accesses
+(TCP_TOTAL_CACHE_ACCESSES_sum), L1 pending stalls, L1 -> L2 read requests, VMEM read instructions and
+VMEM issue cycles per wave cycle = SQ_INST_CYCLES_VMEM_RD / SQ_WAVE_CYCLES.
 Dispatch kinds of one kernel name are told apart by their VGPR count (the instrumented counting
 pt_camera_kernel<true> differs from the timed one).
 """
@@ -65,7 +69,7 @@ def main(tag, workload):
                 per_kind[(r.get("Kernel_Name", ""), r.get("VGPR_Count", "?"))].append(
                     int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
     cnt = defaultdict(lambda: defaultdict(list))  # (name, vgpr) -> counter -> per-dispatch values
-    for sub in ("fetch", "write", "tcc", "sq"):
+    for sub in ("fetch", "write", "tcc", "sq", "ta", "tcp", "sqv"):
         for r in _counters(os.path.join(base, sub)):
             cnt[(r["Kernel_Name"], r.get("VGPR_Count", "?"))][r["Counter_Name"]].append(float(r["Counter_Value"]))
 
@@ -115,6 +119,20 @@ def main(tag, workload):
                                        "fetch_kib": fa, "write_kib": wa, "hbm_bytes_per_launch": hbm,
                                        "hbm_gbs": gbs, "l2_hit": l2, "valu_lane_util": lanes,
                                        "valu_issue_share": issue, "wave_wait_share": wait}
+    vm = [(k, c) for k, c in cnt.items() if "TA_BUSY_avr" in c or "SQ_INSTS_VMEM_RD" in c or "TCP_TOTAL_CACHE_ACCESSES_sum" in c]
+    if vm:
+        lines += ["", "## vector-memory path per dispatch (TA / TCP / SQ-VMEM passes)", "",
+                  "| kernel | VGPRs | TA busy cycles (avr) | TA stalled by TC | buffer read wavefronts | flat read wavefronts | "
+                  "TCP accesses | TCP pending stall | TCP->TCC read req | VMEM rd insts | VMEM rd issue cycles | "
+                  "VMEM cycles / wave cycle | wait-inst / wave cycle |", "|" + "---|" * 13]
+        for (name, vg), c in sorted(vm, key=lambda kv: -avg(kv[1], "SQ_WAVE_CYCLES") if "SQ_WAVE_CYCLES" in kv[1] else 0):
+            lines.append(f"| {name[:80]} | {vg} | {avg(c, 'TA_BUSY_avr'):.1f} | {avg(c, 'TA_ADDR_STALLED_BY_TC_CYCLES_sum'):.4g} | "
+                         f"{avg(c, 'TA_BUFFER_READ_WAVEFRONTS_sum'):.4g} | {avg(c, 'TA_FLAT_READ_WAVEFRONTS_sum'):.4g} | "
+                         f"{avg(c, 'TCP_TOTAL_CACHE_ACCESSES_sum'):.4g} | {avg(c, 'TCP_PENDING_STALL_CYCLES_sum'):.4g} | "
+                         f"{avg(c, 'TCP_TCC_READ_REQ_sum'):.4g} | {avg(c, 'SQ_INSTS_VMEM_RD'):.4g} | "
+                         f"{avg(c, 'SQ_INST_CYCLES_VMEM_RD'):.4g} | "
+                         f"{_div(avg(c, 'SQ_INST_CYCLES_VMEM_RD'), avg(c, 'SQ_WAVE_CYCLES')):.4f} | "
+                         f"{_div(avg(c, 'SQ_WAIT_INST_ANY'), avg(c, 'SQ_WAVE_CYCLES')):.4f} |")
     lines += _two_queue_timeline(base)
     with open(os.path.join(ROOT, "profiles", f"{tag}_summary.md"), "w") as fh:
         fh.write("\n".join(lines) + "\n")

@@ -5,6 +5,12 @@
 #   pass 3: --pmc WRITE_SIZE            (own pass) HBM write side
 #   pass 4: --pmc TCC_HIT_sum TCC_MISS_sum         L2 hit rate
 #   pass 5: --pmc 8 SQ counters                    VALU issue / lane utilisation, wave wait cycles
+#   pass 6: --pmc 2 TA + 2 TCP counters            texture-addresser busy, buffer read wavefronts, L1 accesses, L1 -> L2 reads
+#   pass 7: --pmc 2 TA + 1 TCP counters            TA stalled by the L1, flat read wavefronts, L1 pending stalls
+#   pass 8: --pmc 5 SQ vector-memory counters      VMEM read instructions and issue cycles per wave cycle
+#           (passes 6-8: the path tracer alone, --no-gs: the per-lane vector-memory path of pt_camera_kernel.
+#           Four TA counters in one pass are refused: "Request exceeds the capabilities of the hardware to
+#           collect", and rocprofv3 aborts; two per block per pass)
 # Each pass is its own run (gpurun refuses --pmc with trace domains; counter block limits per pass).
 # Outputs under gpurun_out/prof_<tag>/; summarise with profiles/parse_rocprof.py <tag>.
 set -euo pipefail
@@ -25,4 +31,11 @@ timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -o run --output-for
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d "$OUT/write" -o run --output-format csv -- python3 bench.py $PARGS > "$OUT/bench_write.log" 2>&1
 timeout -k 10 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum -d "$OUT/tcc" -o run --output-format csv -- python3 bench.py $PARGS > "$OUT/bench_tcc.log" 2>&1
 timeout -k 10 300 rocprofv3 --pmc $SQ -d "$OUT/sq" -o run --output-format csv -- python3 bench.py $PARGS > "$OUT/bench_sq.log" 2>&1
+TA="TA_BUSY_avr TA_BUFFER_READ_WAVEFRONTS_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum"
+TCP="TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_FLAT_READ_WAVEFRONTS_sum TCP_PENDING_STALL_CYCLES_sum"
+SQV="SQ_INSTS_VMEM_RD SQ_INST_CYCLES_VMEM_RD SQ_ACTIVE_INST_VMEM SQ_WAIT_INST_ANY SQ_WAVE_CYCLES"
+VARGS="$PARGS --no-gs"
+timeout -k 10 300 rocprofv3 --pmc $TA -d "$OUT/ta" -o run --output-format csv -- python3 bench.py $VARGS > "$OUT/bench_ta.log" 2>&1
+timeout -k 10 300 rocprofv3 --pmc $TCP -d "$OUT/tcp" -o run --output-format csv -- python3 bench.py $VARGS > "$OUT/bench_tcp.log" 2>&1
+timeout -k 10 300 rocprofv3 --pmc $SQV -d "$OUT/sqv" -o run --output-format csv -- python3 bench.py $VARGS > "$OUT/bench_sqv.log" 2>&1
 echo "profiles collected in $OUT"

@@ -3,6 +3,10 @@
 C3 workload, interleaved rounds in ONE process (cdna_hip_programming.md §5.4 rule 24).
 
   python tools/ab_pt.py base w4 ...     (variant "base" = libptgs.so)
+
+AB_SCENE=c5 times C5's mesh instead (the 1M-triangle atrium at 3840x2160, whose tree launches the DEEP
+kernels and whose nodes exceed an XCD's L2); AB_SPP, AB_ROUNDS, AB_CALLS as before. Each variant's image is
+compared with the first variant's first image.
 """
 import os
 import sys
@@ -21,8 +25,9 @@ def main():
     spp = int(os.environ.get("AB_SPP", "16"))
     rounds = int(os.environ.get("AB_ROUNDS", "3"))
     calls = int(os.environ.get("AB_CALLS", "1"))  # consecutive calls per measurement (the viewer: AB_SPP=1 AB_CALLS=64)
-    W, H = 1920, 1080
-    scene = Y.atrium_scene(250_000, seed=2)
+    c5 = os.environ.get("AB_SCENE", "c3") == "c5"
+    W, H = (3840, 2160) if c5 else (1920, 1080)
+    scene = Y.atrium_scene(1_000_000 if c5 else 250_000, seed=2)
     scene.blue_noise = Y.blue_noise(1024)
     pose = Camera(aspect=W / H).look_at([-15.0, 4.0, 5.0], [10.0, 3.0, -3.0])
     rs = {}
