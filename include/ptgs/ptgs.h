@@ -36,7 +36,8 @@ extern "C" {
 #define PTGS_ABI_VERSION 4  /* 3: ptgs_gaussians.ids, ptgs_splat_stats.fused, ptgs_splat_status spill fields;
                              * 4: PTGS_EBADIDS, PTGS_FLAG_SPLAT_OVERLAP. Added since, without a version
                              * change (new functions only): ptgs_gaussians_sh_colors, ptgs_gaussians_activate,
-                             * ptgs_gaussians_permute_sh; ptgs_read_gaussian_ply in ptgs_host.h */
+                             * ptgs_gaussians_permute_sh, ptgs_splat_gaussians_backward (with the struct
+                             * ptgs_gaussian_grads); ptgs_read_gaussian_ply in ptgs_host.h */
 
 /* ---------------- error codes ---------------- */
 #define PTGS_OK 0
@@ -606,6 +607,57 @@ int ptgs_gaussians_activate(ptgs_ctx* ctx, const float* log_scales, const float*
  * (never read out of bounds). */
 int ptgs_gaussians_permute_sh(ptgs_ctx* ctx, const float* sh, uint32_t sh_degree, const uint32_t* ids,
                               uint32_t count, float* out, void* hip_stream);
+
+/* Backward pass of ptgs_splat_gaussians (training): the gradients of a loss with respect to the
+ * Gaussians, given dL/d(out_rgba32f). It consumes the frame the forward left in the context's
+ * workspace, so the context's most recent splat call must have been a complete, full-frame
+ * ptgs_splat_gaussians (tile rows 0, ~0u; not _over, not _views) rendered with PTGS_FLAG_SPLAT_PUBLISH
+ * and stats != NULL for the same count, width and height; the caller guarantees that g, ubo and bg are
+ * that frame's. g->chunk_bounds is ignored; g->ids must be NULL (training does not use reordered copies:
+ * differentiate the original order).
+ *
+ * The function being differentiated is the forward as it stands.
+ * Per Gaussian (gs_preprocess_one):
+ *   culled (every gradient 0) when d = -(view * mean).z <= 0.2, when det == 0, or when its tile rect is empty
+ *   means2d = ndc2pix(ph.xy / (ph.w + 1e-7)), ph = mvp * mean, ndc2pix(v, S) = ((v + 1) S - 1) / 2
+ *   Sigma = R(q/|q|) S^2 R(q/|q|)^T
+ *   cov2d = T Sigma T^T + 0.3 I, T = J W (W: the view's rotation), J = [[fx/d, 0, fx tx/d^2], [0, fy/d, fy ty/d^2]]
+ *           at the clamped point tx = clamp(x/d, +-1.3 tan_fovx) d (ty likewise), (x, y, -d) = view * mean
+ *   conic (a, b, c) = cov2d^-1
+ *   the 3-sigma radius and the rect decide only membership (which tiles hold the Gaussian), the depth
+ *   only order: neither carries a gradient
+ * Per pixel, over its tile's list in sorted order:
+ *   alpha = min(0.99, o exp(power)), power = -(a dx^2 + c dy^2)/2 - b dx dy, (dx, dy) = pixel - means2d
+ *   a pair with alpha < 1/255 is skipped; the pixel stops before the Gaussian that would take T below 1e-4
+ *   out.rgb = sum c alpha T + T_final bg, out.a = 1 - T_final
+ * The gradient is the derivative of exactly this function with every discrete decision (membership,
+ * order, skip, stop, culling) held fixed, and min(0.99, .) and clamp as autograd treats them: a pair
+ * clamped at 0.99 passes gradient to its colour and, through T, to the pairs behind it, but none to its
+ * own opacity, conic or 2D mean; a clamped tx depends on the mean only through d. dL_dout_rgba32f
+ * (device, W*H*4) carries all four channels.
+ *
+ * Stream-ordered on hip_stream. Every non-null array of grads (device pointers) is overwritten (zeroed,
+ * then accumulated into). Scratch (9 floats per Gaussian) belongs to the context's splat workspace;
+ * growing it may synchronise, like the other workspace buffers. The per-tile partial sums are added with
+ * float atomics, so the results are NOT bit-reproducible from run to run (the order of the adds varies).
+ * count == 0: PTGS_OK, nothing is launched. PTGS_EINVAL (message in ptgs_last_error, nothing enqueued): a
+ * null ctx / g / ubo / bg / dL_dout / grads or a null required array, g->ids != NULL, or no matching
+ * published frame (above).
+ * Not covered: ptgs_gaussians_sh_colors and ptgs_gaussians_activate (element-wise: chain them from
+ * grads.colors / scales / opacities), the `over` composite, tile-row shards. */
+typedef struct ptgs_gaussian_grads {
+    float* means;      /* 3N */
+    float* scales;     /* 3N, w.r.t. the linear scales */
+    float* rotations;  /* 4N, w.r.t. the un-normalised quaternion */
+    float* opacities;  /* N  */
+    float* colors;     /* 3N */
+    float* means2d;    /* NULL or 2N: dL/d(pixel position), the densification statistic */
+    float* conics;     /* NULL or 3N: dL/d(conic a, b, c); test / debug access to the blend's own output */
+} ptgs_gaussian_grads;
+int ptgs_splat_gaussians_backward(ptgs_ctx* ctx, const ptgs_gaussians* g, const ptgs_ubo* ubo,
+                                  uint32_t width, uint32_t height, const float bg[3],
+                                  const float* dL_dout_rgba32f, const ptgs_gaussian_grads* grads,
+                                  void* hip_stream);
 
 /* Report of the stream-ordered splat (no stats): waits for hip_stream and the context's view streams,
  * then returns (and clears) the counts since the last query. frames / views[v]: frames left

@@ -146,6 +146,12 @@ class Gaussians(C.Structure):
                 ("chunk_bounds", C.c_void_p)]
 
 
+class GaussianGrads(C.Structure):
+    """ptgs_gaussian_grads: the arrays ptgs_splat_gaussians_backward overwrites (means2d / conics optional)."""
+    _fields_ = [("means", C.c_void_p), ("scales", C.c_void_p), ("rotations", C.c_void_p),
+                ("opacities", C.c_void_p), ("colors", C.c_void_p), ("means2d", C.c_void_p), ("conics", C.c_void_p)]
+
+
 class SplatStats(C.Structure):
     _fields_ = [("num_rendered", C.c_uint32), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32),
                 ("num_visible", C.c_uint32), ("fused", C.c_uint32)]
@@ -212,6 +218,8 @@ SYMBOLS = {
     "ptgs_gaussians_sh_colors": (_I, [_P, _P, _P, _U, _U, _U, _FP, _P, _P]),
     "ptgs_gaussians_activate": (_I, [_P, _P, _P, _U, _P, _P, _P]),
     "ptgs_gaussians_permute_sh": (_I, [_P, _P, _U, _P, _U, _P, _P]),
+    "ptgs_splat_gaussians_backward": (_I, [_P, C.POINTER(Gaussians), C.POINTER(Ubo), _U, _U, _FP, _P,
+                                           C.POINTER(GaussianGrads), _P]),
     "ptgs_trace_depth_rows": (_I, [_P, C.POINTER(Ubo), _U, _U, _U, _U, _P, _P]),
     "ptgs_knn3_mean_dist2": (_I, [_P, _P, _U, _P, _P]),
     "ptgs_gaussians_from_points": (_I, [_P, _P, _P, _U, _P, _P, _P, _P, _P, _P]),

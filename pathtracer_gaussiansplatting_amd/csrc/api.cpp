@@ -32,6 +32,7 @@
 #include "pt_wavefront.h"
 #include "comm.h"
 #include "splat.h"
+#include "splat_backward.h"
 #include "splat_sh.h"
 #include "textures.h"
 
@@ -1047,6 +1048,40 @@ int ptgs_gaussians_permute_sh(ptgs_ctx* c, const float* sh, uint32_t sh_degree, 
   HIPCHK(c, hipSetDevice(c->device));
   const hipError_t e = splat_sh_permute(sh, sh_degree, ids, count, out, (hipStream_t)stream);
   if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_permute_sh: %s", hipGetErrorString(e));
+  return PTGS_OK;
+}
+
+int ptgs_splat_gaussians_backward(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t w, uint32_t h,
+                                  const float bg[3], const float* dL_dout, const ptgs_gaussian_grads* grads,
+                                  void* stream) {
+  if (!c) return PTGS_EINVAL;
+  if (!g || !ubo || !bg || !dL_dout || !grads) return fail(c, PTGS_EINVAL, "null argument");
+  if (g->ids) return fail(c, PTGS_EINVAL, "the backward pass takes the Gaussians in their original order (ids must be NULL)");
+  if (g->count == 0) return PTGS_OK;  // (empty arrays may be null)
+  if (!g->means || !g->scales || !g->rotations || !g->opacities || !g->colors)
+    return fail(c, PTGS_EINVAL, "null gaussian array");
+  if (!grads->means || !grads->scales || !grads->rotations || !grads->opacities || !grads->colors)
+    return fail(c, PTGS_EINVAL, "null gradient array (means2d and conics alone are optional)");
+  if (!is_device_ptr(dL_dout) || !is_device_ptr(grads->means))
+    return fail(c, PTGS_EINVAL, "dL_dout / gradient arrays must be device pointers");
+  if (ubo->proj[0] == 0.0f || ubo->proj[5] == 0.0f) return fail(c, PTGS_EINVAL, "degenerate projection");
+  SplatFrame f;
+  splat_last_frame(c->splat, &f);
+  if (!f.valid)
+    return fail(c, PTGS_EINVAL,
+                "no frame to differentiate: the latest splat call must be a full-frame ptgs_splat_gaussians with "
+                "PTGS_FLAG_SPLAT_PUBLISH and stats");
+  if (f.n != g->count || f.W != w || f.H != h)
+    return fail(c, PTGS_EINVAL, "the latest frame has %u gaussians at %ux%u, the backward call %u at %ux%u", f.n, f.W,
+                f.H, g->count, w, h);
+  HIPCHK(c, hipSetDevice(c->device));
+  float* acc = nullptr;
+  HIPCHK(c, splat_backward_scratch(c->splat, f.n, &acc));
+  float mvp[16];
+  mat4_mul(ubo->proj, ubo->view, mvp);
+  const hipError_t e = splat_gaussians_backward(f, acc, g, ubo->view, mvp, ubo->proj[0], ubo->proj[5], bg, dL_dout, grads,
+                                                (hipStream_t)stream);
+  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_splat_gaussians_backward: %s", hipGetErrorString(e));
   return PTGS_OK;
 }
 

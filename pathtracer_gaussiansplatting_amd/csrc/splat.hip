@@ -29,6 +29,7 @@
 #include "../../include/ptgs/ptgs.h"
 #include "detmath.h"
 #include "splat.h"
+#include "splat_backward.h"
 #include "splat_probe.h"
 
 namespace ptgs {
@@ -65,6 +66,7 @@ struct SplatWorkspace {
   DevBuf crect, sp_keys, sp_vals;  // spilled tiles (gs_spill_tile): chunk rects, the spill pool
   DevBuf fsq;                 // the fused front end's slice queue
   DevBuf cskip;               // per 256-Gaussian chunk: skipped by a tile-row-restricted frame
+  DevBuf grad_acc;            // the backward pass's per-Gaussian sums (splat_backward.hip)
   uint32_t sp_cap = 0;        // spill pool capacity (pairs)
   uint32_t incomplete = 0;    // frames reported incomplete (spill pool exhausted) since the last status clear
   uint32_t spilled_base = 0, incomplete_base = 0;  // device counters fz[9] / fz[10] at the last status clear
@@ -82,6 +84,8 @@ struct SplatWorkspace {
   hipEvent_t k_event = nullptr;
   uint32_t last_n = 0, last_k = 0, last_tiles = 0;
   bool last_published = false;  // the last frame published its sorted keys / values and was synchronised
+  uint32_t last_w = 0, last_h = 0;  // its image size
+  bool last_full = false;       // and it rendered every tile row without the `over` composite (splat_last_frame)
   uint32_t sort_r = 3;        // large-tile radix sort: items per work-item (from the previous frame's largest tile)
   uint32_t sort_grid = 256;   // its workgroups (from the previous frame's large-tile count)
   bool sort_attr = false;     // its dynamic-LDS limit raised
@@ -97,7 +101,7 @@ void splat_workspace_destroy(SplatWorkspace* w) {
                    &w->vals_out, &w->ranges, &w->hist, &w->tile_info, &w->group_total, &w->tile_slots, &w->point_keys,
                    &w->total, &w->rect, &w->large, &w->large_ctr, &w->sort_scratch, &w->cursor, &w->fz,
                    &w->pub_offs, &w->keys_pub, &w->vals_pub, &w->dbg_depths, &w->fzp, &w->nzbuf, &w->order,
-                   &w->crect, &w->sp_keys, &w->sp_vals, &w->fsq, &w->cskip};
+                   &w->crect, &w->sp_keys, &w->sp_vals, &w->fsq, &w->cskip, &w->grad_acc};
   for (DevBuf* b : all)
     if (b->p) (void)hipFree(b->p);
   if (w->k_host) (void)hipHostFree(w->k_host);
@@ -2479,6 +2483,7 @@ hipError_t splat_gaussians(SplatWorkspace* w, const ptgs_gaussians* g, const flo
                            uint32_t* report, const SplatOverlap* ov, SplatSeq* seq) {
   hipError_t e;
   *report = 0;
+  w->last_full = false;  // (a call that fails leaves no frame for the backward pass)
   if (stats || publish || time_stages) ov = nullptr;  // (these frames are synchronous or instrumented: serial)
   if (time_stages && !w->ev[0])
     for (hipEvent_t& ev : w->ev)
@@ -2985,6 +2990,9 @@ hipError_t splat_gaussians(SplatWorkspace* w, const ptgs_gaussians* g, const flo
   w->last_k = K;
   w->last_tiles = tiles;
   w->last_published = publish && stats;
+  w->last_w = W;
+  w->last_h = H;
+  w->last_full = !depth && cam.row_begin == 0 && cam.row_end == cam.grid_y;
   return hipSuccess;
 }
 
@@ -3194,6 +3202,24 @@ void splat_get_buffers(const SplatWorkspace* w, ptgs_splat_buffers* out) {
   out->num_gaussians = w->last_n;
   out->num_rendered = w->last_k;
   out->num_tiles = w->last_tiles;
+}
+
+void splat_last_frame(const SplatWorkspace* w, SplatFrame* out) {
+  out->valid = w->last_published && w->last_full;
+  out->n = w->last_n;
+  out->W = w->last_w;
+  out->H = w->last_h;
+  out->tiles = w->last_tiles;
+  out->sorted_values = (const uint32_t*)(w->last_fused ? w->vals_pub.p : w->vals_out.p);
+  out->ranges = (const uint2*)w->ranges.p;
+  out->rec = (const float4*)w->rec.p;
+  out->radii = (const int*)w->radii.p;
+}
+
+hipError_t splat_backward_scratch(SplatWorkspace* w, uint32_t n, float** acc) {
+  const hipError_t e = ensure(w->grad_acc, (size_t)n * GS_BWD_ACC * 4);
+  *acc = (float*)w->grad_acc.p;
+  return e;
 }
 
 void splat_get_tile_rows(const SplatWorkspace* w, const unsigned long long** rows, uint32_t* cap) {

@@ -1,0 +1,35 @@
+// splat_backward.h — backward pass of the 3DGS rasterizer (see splat_backward.hip).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/ptgs/ptgs.h"
+#include "splat.h"
+
+namespace ptgs {
+
+// The published frame a backward pass consumes: what the workspace's latest splat_gaussians call left
+// (splat.hip fills it). valid: that call was a complete full-frame ptgs_splat_gaussians (no tile-row
+// restriction, no `over` composite) with publish and stats.
+struct SplatFrame {
+  bool valid;
+  uint32_t n, W, H, tiles;
+  const uint32_t* sorted_values;  // the tiles' depth-sorted Gaussians
+  const uint2* ranges;            // per tile: [begin, end) in sorted_values
+  const float4* rec;              // three float4 per Gaussian (gs_preprocess_one)
+  const int* radii;               // 0: culled
+};
+void splat_last_frame(const SplatWorkspace* w, SplatFrame* out);
+// the backward's per-Gaussian accumulator (GS_BWD_ACC floats per Gaussian; grown like the other
+// workspace buffers: growth frees the old one, which waits for the device)
+#define GS_BWD_ACC 9
+hipError_t splat_backward_scratch(SplatWorkspace* w, uint32_t n, float** acc);
+
+// view/mvp column-major float[16]; p00 = proj[0][0], p11 = proj[1][1]; f: the frame (splat_last_frame,
+// valid), acc: splat_backward_scratch(n). Stream-ordered on s.
+hipError_t splat_gaussians_backward(const SplatFrame& f, float* acc, const ptgs_gaussians* g, const float* view,
+                                    const float* mvp, float p00, float p11, const float bg[3], const float* dL_dout,
+                                    const ptgs_gaussian_grads* grads, hipStream_t s);
+
+}  // namespace ptgs

@@ -1,0 +1,249 @@
+// splat_backward.hip — backward pass of the 3DGS rasterizer for gfx950 (ptgs_splat_gaussians_backward).
+//
+// It differentiates the forward of splat.hip as it stands (the contract is stated in ptgs.h) and consumes
+// the frame that forward published: every tile's depth-sorted Gaussians and the per-Gaussian blend records.
+// Two launches:
+//   1. blend backward   one workgroup per 16x16 tile, one pixel per lane (the forward's quadrant-per-wave
+//                       mapping). The records are staged through LDS in batches of 256 in the forward's
+//                       staged form, so z, the alpha >= 1/255 skip and the T < 1e-4 stop are the forward's
+//                       own expressions. Two front-to-back walks: the first recomputes what the forward
+//                       does not keep (the pixel's T_final and, folded into one number, the whole sum
+//                       dL/dC . C + dL/dT_final T_final); the second walks again with the prefix of that
+//                       sum, which gives each pair's suffix without a division by 1 - alpha per step, and
+//                       reduces the pair's nine partial sums over the wave in DPP, over the four waves
+//                       through LDS (per chunk of 64 staged pairs), and adds them to a per-Gaussian
+//                       accumulator with one f32 atomic per value per (tile, Gaussian). A wave walks only
+//                       the pairs whose alpha box reaches its quadrant, and skips by ballot a pair none of
+//                       its lanes evaluates.
+//   2. project backward one work-item per Gaussian: the accumulator -> colours, opacity, (2D mean, conic)
+//                       and, through conic = cov^-1, cov = T Sigma T^T + 0.3 I, T = J W, Sigma = R S^2 R^T,
+//                       q / |q|, the 3D mean, the scales and the rotation. Plain f32.
+// Float atomics: the sums depend on the arrival order, so the gradients are not bit-reproducible.
+#include <hip/hip_runtime.h>
+
+#include "../../include/ptgs/ptgs.h"
+#include "detmath.h"
+#include "splat_backward.h"
+#include "splat_backward_math.h"
+
+namespace ptgs {
+
+#define GB_BLOCK 256
+#define GB_TILE 16
+#define GB_CHUNK 64  // staged pairs per reduction round: a wave's ballot; 23 KiB of LDS, 7 waves per SIMD (256:
+                     // 50 KiB, 3 waves per SIMD, 0.50 vs 0.37 ms at C2)
+#define GB_L2E 1.4426950408889634f
+#define GB_LN2 0.69314718055994531f
+static_assert(GS_BWD_ACC == 9, "2D mean x2, staged quadratic A B C, log2 opacity, colour x3");
+
+// Wave64 float sum in DPP (row_shr 1/2/4/8 inside rows of 16, then row_bcast 15 / 31): lane 63 ends with
+// the sum of all 64, returned wave-uniform. Every lane of the wave must be active.
+__device__ __forceinline__ float gb_wave_sum(float v) {
+  auto step = [](float x, int y) { return x + __int_as_float(y); };
+  v = step(v, __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xF, 0xF, false));  // row_shr:1
+  v = step(v, __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x112, 0xF, 0xF, false));  // row_shr:2
+  v = step(v, __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xF, 0xF, false));  // row_shr:4
+  v = step(v, __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xF, 0xF, false));  // row_shr:8
+  v = step(v, __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xA, 0xF, false));  // row_bcast:15
+  v = step(v, __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xC, 0xF, false));  // row_bcast:31
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
+// acc: per Gaussian (d gx, d gy, dA, dB, dC, dL, d r, d g, d b) for the staged z = A dx^2 + B dx dy +
+// C dy^2 + L (dx, dy: pixel - 2D mean; A = -a/2 log2e, B = -b log2e, C = -c/2 log2e, L = log2 o).
+__global__ __launch_bounds__(GB_BLOCK) void gs_blend_backward_kernel(uint32_t W, uint32_t H, uint32_t grid_x,
+                                                                      const uint2* __restrict__ ranges,
+                                                                      const uint32_t* __restrict__ vals,
+                                                                      const float4* __restrict__ rec, float bg_r,
+                                                                      float bg_g, float bg_b,
+                                                                      const float4* __restrict__ dout,
+                                                                      float* __restrict__ acc) {
+  __shared__ float4 s_stage[3 * GB_BLOCK];  // (A, B, C, D) (E, F, r, g) (b, gx, gy, -): see the forward's stage_rec
+  __shared__ __attribute__((aligned(16))) float s_red[4][GB_CHUNK * GS_BWD_ACC];  // per wave, per pair of a chunk
+  __shared__ uint32_t s_gid[GB_BLOCK];
+  __shared__ uint8_t s_mask[GB_BLOCK];
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+  const uint32_t tile = blockIdx.x, tile_y = tile / grid_x, tile_x = tile - tile_y * grid_x;
+  const uint2 range = ranges[tile];
+  const uint32_t n = range.y - range.x;
+  if (n == 0) return;  // (uniform)
+  const float tx0 = (float)(tile_x * GB_TILE), ty0 = (float)(tile_y * GB_TILE);
+  const uint32_t px = tile_x * GB_TILE + (wave & 1u) * 8u + (lane & 7u);
+  const uint32_t py = tile_y * GB_TILE + (wave >> 1) * 8u + (lane >> 3);
+  const bool inside = px < W && py < H;
+  const float4 go = inside ? dout[(size_t)py * W + px] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  const float ux = (float)px - tx0, uy = (float)py - ty0, uxx = ux * ux, uxy = ux * uy, uyy = uy * uy;
+  // out.rgb = C + T_final bg, out.a = 1 - T_final: dL/dT_final
+  const float g_tf = ((go.x * bg_r + go.y * bg_g) + go.z * bg_b) - go.w;
+  float total = 0.0f;  // sum over the pixel's pairs of wgt (c . dL/dC), + T_final dL/dT_final
+  for (int pass = 0; pass < 2; ++pass) {
+    float T = 1.0f, prefix = 0.0f;
+    bool done = !inside;
+    for (uint32_t base = 0; base < n; base += GB_BLOCK) {
+      // (every wave is done with the previous batch's records and sums)
+      if (__syncthreads_count(done) == GB_BLOCK) break;
+      const uint32_t idx = base + tid;
+      if (idx < n) {
+        const uint32_t g = vals[range.x + idx];
+        const float4 ga = rec[3 * g], gb = rec[3 * g + 1], gc = rec[3 * g + 2];
+        // the forward's staged quadratic in tile-local pixel coordinates (same expressions: same z)
+        const float gx = ga.x - tx0, gy = ga.y - ty0, A = ga.z, B = ga.w, C = gb.x;
+        const float D = -2.0f * A * gx - B * gy, E = -B * gx - 2.0f * C * gy;
+        const float F = ((A * gx * gx + B * gx * gy) + C * gy * gy) + gb.y;
+        s_stage[3 * tid] = make_float4(A, B, C, D);
+        s_stage[3 * tid + 1] = make_float4(E, F, gb.z, gb.w);
+        s_stage[3 * tid + 2] = make_float4(gc.x, gx, gy, 0.0f);
+        s_gid[tid] = g;
+        // the forward's quadrant mask of the record's alpha box (gc.y, gc.z: the half-extents outside
+        // which alpha < 1/255): bit q = (x half q & 1, y half q >> 1), wave q's pixels
+        const float x0 = gx - gc.y, x1 = gx + gc.y, y0 = gy - gc.z, y1 = gy + gc.z;
+        const bool xl = x0 <= 7.0f && x1 >= 0.0f, xr = x0 <= 15.0f && x1 >= 8.0f;
+        const bool yt = y0 <= 7.0f && y1 >= 0.0f, yb = y0 <= 15.0f && y1 >= 8.0f;
+        s_mask[tid] = (uint8_t)((uint32_t)(xl && yt) | ((uint32_t)(xr && yt) << 1) | ((uint32_t)(xl && yb) << 2) |
+                                ((uint32_t)(xr && yb) << 3));
+      }
+      __syncthreads();
+      const uint32_t nb = min((uint32_t)GB_BLOCK, n - base);
+      // chunks of GB_CHUNK staged pairs: the wave walks the chunk's pairs whose box reaches its quadrant (a
+      // ballot of the masks, in sorted order), and the second walk reduces and sends its sums per chunk (the
+      // sums' LDS is what bounds the workgroups per CU)
+      for (uint32_t c0 = 0; c0 < nb; c0 += GB_CHUNK) {
+        const uint32_t c1 = min(nb, c0 + GB_CHUNK);
+        if (pass) {  // the wave's sums of this chunk start at zero: a pair it skips costs nothing more
+          if (c0) __syncthreads();  // (the previous chunk's sums have been read)
+          float4* z4 = reinterpret_cast<float4*>(s_red[wave]);
+          for (uint32_t k = lane; k < GB_CHUNK * GS_BWD_ACC / 4; k += 64) z4[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+        unsigned long long todo = __builtin_amdgcn_ballot_w64(c0 + lane < c1 && ((s_mask[c0 + lane] >> wave) & 1u));
+        while (todo) {
+          if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;  // every pixel of the wave has stopped
+          const uint32_t k = (uint32_t)__builtin_ctzll(todo), j = c0 + k;
+          todo &= todo - 1ull;
+          const float4 a = s_stage[3 * j], b = s_stage[3 * j + 1], c = s_stage[3 * j + 2];
+          const float z = __builtin_fmaf(a.x, uxx, __builtin_fmaf(a.y, uxy, __builtin_fmaf(a.z, uyy,
+                                         __builtin_fmaf(a.w, ux, __builtin_fmaf(b.x, uy, b.y)))));
+          bool valid = z >= -7.9943534f && !done;  // alpha >= 1/255
+          if (__builtin_amdgcn_ballot_w64(valid) == 0ull) continue;  // no lane of the wave evaluates the pair
+          const float e = __builtin_amdgcn_exp2f(z);
+          const float alpha = valid ? fminf(0.99f, e) : 0.0f;
+          float wgt = alpha * T;
+          float test_T = T - wgt;
+          if (test_T < 0.0001f) {  // this Gaussian would saturate the pixel: stop before it
+            done = true;
+            valid = false;
+            wgt = 0.0f;
+            test_T = T;
+          }
+          const float cdot = (b.z * go.x + b.w * go.y) + c.x * go.z;
+          if (!pass) {
+            total += wgt * cdot;
+          } else {
+            prefix += wgt * cdot;
+            if (__builtin_amdgcn_ballot_w64(valid) != 0ull) {  // (uniform: every lane takes part in the sums)
+              // dL/dalpha = T (c . dL/dC) - (what lies behind the pair) / (1 - alpha); the 0.99 clamp
+              // passes nothing to z
+              const float behind = total - prefix;
+              const float dalpha = T * cdot - behind / (1.0f - alpha);
+              const float dz = (valid && e <= 0.99f) ? dalpha * alpha * GB_LN2 : 0.0f;
+              const float dx = ux - c.y, dy = uy - c.z;
+              const float v0 = dz * (-2.0f * a.x * dx - a.y * dy), v1 = dz * (-a.y * dx - 2.0f * a.z * dy);
+              const float s0 = gb_wave_sum(v0), s1 = gb_wave_sum(v1);
+              const float s2 = gb_wave_sum(dz * dx * dx), s3 = gb_wave_sum(dz * dx * dy), s4 = gb_wave_sum(dz * dy * dy);
+              const float s5 = gb_wave_sum(dz);
+              const float s6 = gb_wave_sum(wgt * go.x), s7 = gb_wave_sum(wgt * go.y), s8 = gb_wave_sum(wgt * go.z);
+              if (lane == 63) {
+                float* r = &s_red[wave][k * GS_BWD_ACC];
+                r[0] = s0; r[1] = s1; r[2] = s2; r[3] = s3; r[4] = s4; r[5] = s5; r[6] = s6; r[7] = s7; r[8] = s8;
+              }
+            }
+          }
+          T = test_T;
+        }
+        if (pass) {
+          __syncthreads();
+          // the four waves' sums, one atomic per value per (tile, Gaussian): consecutive lanes add the
+          // consecutive values of a Gaussian; a value no pixel of the tile contributed to is not sent
+          for (uint32_t i = tid; i < (c1 - c0) * GS_BWD_ACC; i += GB_BLOCK) {
+            const float s = (s_red[0][i] + s_red[1][i]) + (s_red[2][i] + s_red[3][i]);
+            const uint32_t slot = i / GS_BWD_ACC;
+            if (s != 0.0f)
+              (void)unsafeAtomicAdd(acc + (size_t)s_gid[c0 + slot] * GS_BWD_ACC + (i - slot * GS_BWD_ACC), s);
+          }
+        }
+      }
+    }
+    if (!pass) total += T * g_tf;
+  }
+}
+
+struct GbOut {
+  float *means, *scales, *rots, *opac, *colors, *means2d, *conics;
+};
+
+__global__ __launch_bounds__(256) void gs_project_backward_kernel(GbCam cam, const float* __restrict__ means,
+                                                                   const float* __restrict__ scales,
+                                                                   const float* __restrict__ rots,
+                                                                   const float* __restrict__ opac, uint32_t n,
+                                                                   const int* __restrict__ radii,
+                                                                   const float* __restrict__ acc, GbOut out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const bool visible = radii[i] > 0;  // (a culled Gaussian is in no tile's list: its sums are zero)
+  const float* s9 = acc + (size_t)i * GS_BWD_ACC;
+  const float dgx = s9[0], dgy = s9[1];
+  const float da = -0.5f * GB_L2E * s9[2], db = -GB_L2E * s9[3], dc = -0.5f * GB_L2E * s9[4];
+  const float o = opac[i];
+  out.opac[i] = (visible && o > 0.0f) ? s9[5] / (o * GB_LN2) : 0.0f;
+  out.colors[3 * i] = s9[6];
+  out.colors[3 * i + 1] = s9[7];
+  out.colors[3 * i + 2] = s9[8];
+  if (out.means2d) {
+    out.means2d[2 * i] = dgx;
+    out.means2d[2 * i + 1] = dgy;
+  }
+  if (out.conics) {
+    out.conics[3 * i] = da;
+    out.conics[3 * i + 1] = db;
+    out.conics[3 * i + 2] = dc;
+  }
+  float dm[3] = {0.0f, 0.0f, 0.0f}, dsc[3] = {0.0f, 0.0f, 0.0f}, dq[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (visible)
+    gs_project_backward_one(cam, means + 3 * i, scales + 3 * i, rots + 4 * i, dgx, dgy, da, db, dc, dm, dsc, dq);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    out.means[3 * i + k] = dm[k];
+    out.scales[3 * i + k] = dsc[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) out.rots[4 * i + k] = dq[k];
+}
+
+hipError_t splat_gaussians_backward(const SplatFrame& f, float* acc, const ptgs_gaussians* g, const float* view,
+                                    const float* mvp, float p00, float p11, const float bg[3], const float* dL_dout,
+                                    const ptgs_gaussian_grads* grads, hipStream_t s) {
+  const uint32_t n = f.n;
+  hipError_t e;
+  if ((e = hipMemsetAsync(acc, 0, (size_t)n * GS_BWD_ACC * 4, s))) return e;
+  GbCam cam;
+  for (int k = 0; k < 16; ++k) {
+    cam.view[k] = view[k];
+    cam.mvp[k] = mvp[k];
+  }
+  cam.fx = p00 * (float)f.W * 0.5f;
+  cam.fy = p11 * (float)f.H * 0.5f;
+  cam.limx = 1.3f * (1.0f / p00);
+  cam.limy = 1.3f * (1.0f / (p11 < 0.0f ? -p11 : p11));
+  cam.W = f.W;
+  cam.H = f.H;
+  cam.grid_x = (f.W + GB_TILE - 1) / GB_TILE;
+  hipLaunchKernelGGL(gs_blend_backward_kernel, dim3(f.tiles), dim3(GB_BLOCK), 0, s, f.W, f.H, cam.grid_x, f.ranges,
+                     f.sorted_values, f.rec, bg[0], bg[1], bg[2], (const float4*)dL_dout, acc);
+  if ((e = hipGetLastError())) return e;
+  const GbOut out = {grads->means, grads->scales, grads->rotations, grads->opacities, grads->colors, grads->means2d,
+                     grads->conics};
+  hipLaunchKernelGGL(gs_project_backward_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, cam, g->means, g->scales,
+                     g->rotations, g->opacities, n, f.radii, (const float*)acc, out);
+  return hipGetLastError();
+}
+
+}  // namespace ptgs

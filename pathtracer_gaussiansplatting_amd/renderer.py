@@ -257,6 +257,34 @@ class Renderer:
         self._chk(rc, "ptgs_splat_gaussians")
         return st if want_stats else None
 
+    def splat_gaussians_backward(self, g: dict, ubo: Ubo, width: int, height: int, dL_dout, bg=(0.0, 0.0, 0.0),
+                                 want_means2d: bool = False, want_conics: bool = False, stream=None) -> dict:
+        """ptgs_splat_gaussians_backward: the gradients of the latest frame, which must be a full-frame
+        splat_gaussians(g, ubo, width, height, ..., bg, want_stats=True) of a renderer that publishes
+        (FLAG_SPLAT_PUBLISH). dL_dout: float32 [H, W, 4]. Returns new tensors "means", "scales" (linear),
+        "rotations" (un-normalised), "opacities", "colors" and, when asked for, "means2d" (dL/d pixel
+        position) and "conics" (dL/d conic a, b, c). Stream-ordered; not bit-reproducible (float atomics)."""
+        import torch
+        n = int(g["means"].shape[0])
+        self._f32(("means", g["means"], n * 3), ("scales", g["scales"], n * 3), ("rotations", g["rotations"], n * 4),
+                  ("opacities", g["opacities"], n), ("colors", g["colors"], n * 3),
+                  ("dL_dout", dL_dout, width * height * 4))
+        dev = g["means"].device
+        shapes = {"means": (n, 3), "scales": (n, 3), "rotations": (n, 4), "opacities": (n,), "colors": (n, 3)}
+        if want_means2d:
+            shapes["means2d"] = (n, 2)
+        if want_conics:
+            shapes["conics"] = (n, 3)
+        out = {k: torch.empty(s, dtype=torch.float32, device=dev) for k, s in shapes.items()}
+        gr = _abi.GaussianGrads()
+        for k, t in out.items():
+            setattr(gr, k, _ptr(t))
+        bgc = np.asarray(bg, np.float32)
+        rc = self.lib.ptgs_splat_gaussians_backward(self._h, C.byref(_gaussians(g)), C.byref(ubo), width, height,
+                                                    _abi.fptr(bgc), _ptr(dL_dout), C.byref(gr), _stream(stream))
+        self._chk(rc, "ptgs_splat_gaussians_backward")
+        return out
+
     def splat_gaussians_views(self, g: dict, ubos, width: int, height: int, outs, bg=(0.0, 0.0, 0.0), stream=None):
         """ptgs_splat_gaussians_views: len(ubos) views of the same Gaussians in one stream-ordered call
         (outs: one RGBA32F[H, W, 4] device tensor per view)."""
