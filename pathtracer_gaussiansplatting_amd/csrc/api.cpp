@@ -513,6 +513,19 @@ int ptgs_scene_upload(ptgs_ctx* c, const ptgs_scene_desc* d) {
     std::vector<uint32_t> n64;
     if (!quantize_bvh4(host_n4.data(), c->info.num_bvh_nodes, n64))
       return fail(c, PTGS_ERANGE, "BVH node extents beyond the compact nodes' step range (2^-100 .. 2^100)");
+    // Their links are re-encoded into the fewest bits this tree needs, so that a stack entry of the
+    // closest-hit walk carries the child's entry distance in the bits left (bvh.h stack_layout,
+    // stack_key.h). PTGS_PT_STACK_KEY_BITS forces the key's width (tests: 0 = never cull).
+    int force = -1;
+    if (const char* e = getenv("PTGS_PT_STACK_KEY_BITS")) force = std::max(0, atoi(e));
+    const StackLayout sl = stack_layout(host_n4.data(), c->info.num_bvh_nodes, force);
+    pack_links64(n64, c->info.num_bvh_nodes, sl);
+    s.stk_key_mask = sl.key_mask;
+    s.leaf_shift = sl.leaf_shift;
+    s.leaf_start_mask = sl.leaf_start_mask;
+    if (getenv("PTGS_BVH_LOG"))
+      fprintf(stderr, "[ptgs] stack word:%u link bits, %u key bits (mask %08x), leaf shift %u\n", sl.ref_bits, sl.key_bits,
+              sl.key_mask, sl.leaf_shift);
     if ((rc = upload(c, (const uint4*)n64.data(), n64.size() / 4, &s.nodes64))) return rc;
   }
   // a zero vertex/index count still needs valid (never dereferenced) pointers

@@ -377,4 +377,40 @@ bool quantize_bvh4(const float* n4, uint32_t num, std::vector<uint32_t>& out) {
   return true;
 }
 
+static uint32_t bits_for(uint32_t v) {  // bits that hold 0 .. v
+  uint32_t b = 0;
+  while (v) { ++b; v >>= 1; }
+  return b;
+}
+
+StackLayout stack_layout(const float* n4, uint32_t num, int force_key_bits) {
+  uint32_t max_start = 0, max_cm1 = 0;
+  for (uint32_t i = 0; i < num; ++i)
+    for (int j = 0; j < 4; ++j) {
+      int32_t link;
+      std::memcpy(&link, &n4[32 * (size_t)i + 24 + j], 4);
+      if (link >= 0) continue;
+      const uint32_t L = ~(uint32_t)link;
+      max_start = std::max(max_start, L & 0x07ffffffu);
+      max_cm1 = std::max(max_cm1, L >> 27);
+    }
+  StackLayout l;
+  l.leaf_shift = bits_for(max_start);
+  l.leaf_start_mask = (1u << l.leaf_shift) - 1u;  // (leaf_shift <= 27)
+  const uint32_t payload = std::max(bits_for(num), l.leaf_shift + bits_for(max_cm1));  // <= 31
+  l.ref_bits = payload + 1u;
+  const uint32_t room = 32u - l.ref_bits;
+  l.key_bits = force_key_bits >= 0 ? std::min((uint32_t)force_key_bits, room) : (room >= PTGS_STACK_KEY_MIN ? room : 0u);
+  l.key_mask = stack_key_mask(l.key_bits);
+  return l;
+}
+
+void pack_links64(std::vector<uint32_t>& n64, uint32_t num, const StackLayout& l) {
+  for (uint32_t i = 0; i < num; ++i)
+    for (int j = 0; j < 4; ++j) {
+      uint32_t& w = n64[PTGS_NODE64_DWORDS * (size_t)i + 12 + j];
+      w = stack_link_pack((int32_t)w, l);
+    }
+}
+
 }  // namespace ptgs

@@ -15,6 +15,8 @@
 #include <stdint.h>
 #include <vector>
 
+#include "stack_key.h"
+
 namespace ptgs {
 
 struct BuildTri {
@@ -58,5 +60,19 @@ void collapse_bvh4(const std::vector<float>& nodes2, std::vector<float>& nodes4,
 // tmax = 1e4 has).
 #define PTGS_NODE64_DWORDS 16
 bool quantize_bvh4(const float* nodes4, uint32_t num_nodes, std::vector<uint32_t>& out);
+
+// The megakernel's packed stack word (stack_key.h): the fewest link bits this tree needs (the node count,
+// so that the all-ones payload the walk uses for "done" is no index; largest first triangle and leaf count
+// among its links; one flag), the rest of the 32 bits to the distance key. Fewer than PTGS_STACK_KEY_MIN
+// key bits (not even the whole exponent: bounds a factor of 4 or more apart) are not worth a compare per
+// pop: such a tree gets 0, and its walk never culls.
+// force_key_bits >= 0 overrides the choice (clamped to what the links leave; the upload's
+// PTGS_PT_STACK_KEY_BITS, for tests).
+#define PTGS_STACK_KEY_MIN 8
+StackLayout stack_layout(const float* nodes4, uint32_t num_nodes, int force_key_bits = -1);
+// Rewrites the compact nodes' links [12..15] (canonical after quantize_bvh4) to packed links, which the
+// megakernel's traversals read: an interior index stays, a leaf becomes flag | first | (count - 1) <<
+// leaf_shift, the empty slots' 0 stays.
+void pack_links64(std::vector<uint32_t>& nodes64, uint32_t num_nodes, const StackLayout& layout);
 
 }  // namespace ptgs

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include "detmath.h"
 #include "texture.h"
+#include "stack_key.h"
 #include "../../include/ptgs/ptgs.h"
 
 namespace ptgs {
@@ -49,6 +50,11 @@ struct DevScene {
   uint32_t num_plights;
   int32_t bn_size;
   int32_t has_transparent;
+  // the compact nodes' packed links and the closest-hit walk's stack word (stack_key.h, bvh.h stack_layout):
+  // wave-uniform, so the masks and the shift are scalar operands
+  uint32_t stk_key_mask;          // the distance key's bits in a stack entry (0: no key, nothing is culled)
+  uint32_t leaf_shift;            // packed leaf: flag | first triangle | (count - 1) << leaf_shift
+  uint32_t leaf_start_mask;       // (1 << leaf_shift) - 1
 };
 
 // UBO fields the shaders read (raytracing.glsl:111-125), with the two matrix inverses the
@@ -117,7 +123,9 @@ __device__ __forceinline__ void pt_lanes_flush(const PtLaneCounts& c) {
 // 1M-triangle atrium 40 (tools/native/bvh_need.cpp): both keep 3-triangle leaves and 4-wide nodes.
 // The overflow is compiled only into the DEEP kernel instantiations (DevScene::deep_stack: need >=
 // PTGS_STACK), launched for C5's tree; C3's runs the LDS-only traversal (the overflow's test per push /
-// pop cost 3.4% on C3 even unused, tools/ab_pt.py).
+// pop cost 3.4% on C3 even unused, tools/ab_pt.py). An entry is 4 B and the LDS cannot grow (it is the
+// occupancy limit), so the megakernel's closest-hit walk packs link and entry distance into the one word
+// (stack_key.h; trace_closest below), in LDS and in the overflow alike.
 #ifndef PTGS_STACK
 #define PTGS_STACK 39
 #endif
@@ -255,12 +263,25 @@ __device__ __noinline__ bool anyhit_accept_call(const DevScene& sc, uint32_t mes
 // ---------------------------------------------------------------------------------------------
 // Traversal
 // ---------------------------------------------------------------------------------------------
-template <bool STATS, bool TEX, bool AH_CALL = false>
+// A leaf link's triangles. PK: a packed link of the compact nodes (stack_key.h: the count sits right above
+// the first triangle's bits, both wave-uniform in width; key bits already cleared), else the canonical one.
+template <bool PK>
+__device__ __forceinline__ void leaf_range(const DevScene& sc, int leaf, uint32_t& start, uint32_t& count) {
+  if (PK) {
+    start = (uint32_t)leaf & sc.leaf_start_mask;
+    count = (((uint32_t)leaf & 0x7fffffffu) >> sc.leaf_shift) + 1u;
+  } else {
+    const uint32_t L = (uint32_t)(~leaf);
+    start = L & 0x07ffffffu;
+    count = (L >> 27) + 1u;
+  }
+}
+
+template <bool STATS, bool TEX, bool AH_CALL = false, bool PK = false>
 __device__ __forceinline__ void leaf_closest(const DevScene& sc, const Ray& r, int leaf, Hit& h,
                                              uint32_t seed, TraversalCounters& cnt) {
-  uint32_t L = (uint32_t)(~leaf);
-  uint32_t start = L & 0x07ffffffu;
-  uint32_t count = (L >> 27) + 1u;
+  uint32_t start, count;
+  leaf_range<PK>(sc, leaf, start, count);
   // the next triangle's 48 B are in flight while this one is tested (+3%)
   float4 na = sc.tris[3u * start], nb = sc.tris[3u * start + 1u], nc = sc.tris[3u * start + 2u];
   for (uint32_t k = 0; k < count; ++k) {
@@ -451,18 +472,36 @@ __device__ __forceinline__ int enter_box4(Box4& b, Push push, Pop pop) {
   cswap4(b, 0, 1); cswap4(b, 2, 3); cswap4(b, 0, 2); cswap4(b, 1, 3); cswap4(b, 1, 2);
   // (the sorted hits come first: at least 4 / 3 / 2 of the four children hit, as lane masks)
   const unsigned long long a01 = h0 & h1, o01 = h0 | h1, a23 = h2 & h3, o23 = h2 | h3;
-  if (__builtin_amdgcn_inverse_ballot_w64(a01 & a23)) push(b.c[3]);
-  if (__builtin_amdgcn_inverse_ballot_w64((a01 & o23) | (o01 & a23))) push(b.c[2]);
-  if (__builtin_amdgcn_inverse_ballot_w64(a01 | a23 | (o01 & o23))) push(b.c[1]);
+  // (each push gets the child's entry distance: the culling walk keeps its floor in the stack word)
+  if (__builtin_amdgcn_inverse_ballot_w64(a01 & a23)) push(b.c[3], b.tn[3]);
+  if (__builtin_amdgcn_inverse_ballot_w64((a01 & o23) | (o01 & a23))) push(b.c[2], b.tn[2]);
+  if (__builtin_amdgcn_inverse_ballot_w64(a01 | a23 | (o01 & o23))) push(b.c[1], b.tn[1]);
   return b.c[0];
 }
 
 // SS: the LDS stack's stride (work-items sharing it); OVF: overflow entries beyond the LDS part (0 for
 // a tree whose stack need fits PTGS_STACK: the overflow's branches and scratch cost 3.4% on C3)
-// N64: fetch the compact nodes (box4_q)
-template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF, bool N64 = false>
+// N64: fetch the compact nodes (box4_q); their links are packed (stack_key.h): an interior index as it is,
+// a leaf with its count right above the first triangle's bits, so that the link takes the fewest bits the
+// tree needs (C3: 21, C5: 23) and the sign still tells a leaf.
+// CULL (with N64; PTGS_PT_STACK_CULL): a pushed entry keeps, in the bits the link leaves free, the floor of
+// the child's entry distance tn from the box test that pushed it (one v_and_or_b32 per push). pop() drops
+// every entry whose bound is > h.t * 1.0000004f: the box test that pushed it, repeated with today's h.t,
+// would miss (tf <= h.t, and the bound is <= tn), so the node fetch, its four box tests and the leaf's
+// triangles are skipped for one LDS read, an AND and a compare. The comparison is strict: a triangle at
+// t == h.t with a lower gid is still found. Any candidate at t lies in its subtree's box, whose stored tn is
+// <= t, so no culled entry holds a candidate with t <= h.t: hits, ray counts and the image are
+// those of the walk that does not cull. A key of 0 bits (sc.stk_key_mask 0) bounds every entry by 0.0 and
+// never culls. trace_any has a constant cap and never culls. C3 at 64 spp, interleaved (tools/ab_pt.py):
+// 5 781 Mrays/s without, 6 048 with (closest-hit node steps 356.9 M -> 288.1 M wave iterations); a pop()
+// that tests the empty stack as a second loop exit instead of popping DONE as a never-culled word: 5 886.
+#ifndef PTGS_PT_STACK_CULL
+#define PTGS_PT_STACK_CULL 1
+#endif
+template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF, bool N64 = false, bool CULL = false>
 __device__ __forceinline__ Hit trace_closest(const DevScene& sc, const Ray& r, uint32_t seed, int* stack,
                                              TraversalCounters& cnt) {
+  static_assert(!CULL || N64, "the distance key needs the compact nodes' packed links");
   Hit h; h.t = r.tmax; h.u = 0.f; h.v = 0.f; h.gid = 0xffffffffu; h.slot = 0;
   const Ray rq = node64_ray<N64>(r);
   int sp = 0;
@@ -472,18 +511,34 @@ __device__ __forceinline__ Hit trace_closest(const DevScene& sc, const Ray& r, u
   // runs with more lanes busy (+2% Mrays/s on C3, tools/ab_pt.py; packing the slab FMAs of child
   // pairs into v_pk_fma_f32 measured -1.4%). The closest hit is the minimum over (t, gid) of every
   // candidate, so visiting order changes neither the hit nor the image.
-  const int DONE = 0x7fffffff;
+  // (culling walk: DONE is a word with the key's bits clear, so the empty stack pops as an entry bounded by 0.0
+  // and pop()'s loop has one exit; no interior index reaches it: bvh.cpp stack_layout)
+  const uint32_t kmask = sc.stk_key_mask;
+  const int DONE = CULL ? (int)(0x7fffffffu & ~kmask) : 0x7fffffff;
   int leaf = DONE;
   int ovf[OVF > 0 ? OVF : 1];  // entries beyond the LDS part (private: scratch)
-  auto push = [&](int x) {
+  auto push = [&](int c, float tn) {
+    const int x = CULL ? (int)stack_pack((uint32_t)c, tn, kmask) : c;
     if (OVF == 0 || sp < PTGS_STACK) stack[sp * SS] = x;
     else ovf[sp - PTGS_STACK] = x;
     ++sp;
   };
   auto pop = [&]() -> int {
-    if (!sp) return DONE;
-    --sp;
-    return (OVF == 0 || sp < PTGS_STACK) ? stack[sp * SS] : ovf[sp - PTGS_STACK];
+    if (!CULL) {
+      if (!sp) return DONE;
+      --sp;
+      return (OVF == 0 || sp < PTGS_STACK) ? stack[sp * SS] : ovf[sp - PTGS_STACK];
+    }
+    const float cap = h.t * 1.0000004f;
+    uint32_t x;
+    do {
+      x = (uint32_t)DONE;
+      if (sp) {
+        --sp;
+        x = (uint32_t)((OVF == 0 || sp < PTGS_STACK) ? stack[sp * SS] : ovf[sp - PTGS_STACK]);
+      }
+    } while (stack_bound(x, kmask) > cap);
+    return (int)stack_link(x, kmask);
   };
   // (a register-cached stack top that hides the LDS read behind the node fetch measured -0.8%)
   for (;;) {
@@ -504,11 +559,11 @@ __device__ __forceinline__ Hit trace_closest(const DevScene& sc, const Ray& r, u
     }
     if (leaf != DONE) {
       PT_LANE_TICK(cnt, PT_L_LEAF);
-      leaf_closest<STATS, TEX>(sc, r, leaf, h, seed, cnt);
+      leaf_closest<STATS, TEX, false, N64>(sc, r, leaf, h, seed, cnt);
       leaf = DONE;
     }
     if (node < 0) {
-      leaf_closest<STATS, TEX>(sc, r, node, h, seed, cnt);
+      leaf_closest<STATS, TEX, false, N64>(sc, r, node, h, seed, cnt);
       node = pop();
     }
     if (node == DONE) return h;
@@ -555,9 +610,8 @@ __device__ __forceinline__ bool trace_any(const DevScene& sc, const Ray& r, uint
       }
       node = next;
     }
-    uint32_t L = (uint32_t)(~node);
-    uint32_t start = L & 0x07ffffffu;
-    uint32_t count = (L >> 27) + 1u;
+    uint32_t start, count;
+    leaf_range<N64>(sc, node, start, count);  // (the compact nodes' links are packed)
     for (uint32_t k = 0; k < count; ++k) {
       PT_LANE_TICK(cnt, PT_L_ANY_TRI);
       const float4* tp = sc.tris + 3u * (start + k);

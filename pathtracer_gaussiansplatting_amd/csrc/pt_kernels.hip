@@ -182,7 +182,8 @@ __global__ __launch_bounds__(PTGS_PT_WG, PTGS_PT_MIN_WAVES) void pt_camera_kerne
         p.depth = depth;
         Ray ray = make_ray(ro, rd, 0.001f, 10000.0f);
         ext_rays++;
-        Hit h = trace_closest<STATS, TEX, PTGS_PT_WG, DEEP ? PTGS_STACK_OVF : 0, PTGS_PT_NODE64 != 0>(sc, ray, p.seed, c.stack, tc);
+        Hit h = trace_closest<STATS, TEX, PTGS_PT_WG, DEEP ? PTGS_STACK_OVF : 0, PTGS_PT_NODE64 != 0,
+                              PTGS_PT_NODE64 != 0 && PTGS_PT_STACK_CULL != 0>(sc, ray, p.seed, c.stack, tc);
         if (STATS && h.gid != 0xffffffffu) tc.hits++;
         ShadowQuery q;
         q.flags = 0;

@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256, wf_min_waves(PTGS_WF_LDS_EXT)) void pt_wf_exte
   Ray r = make_ray(mk3(0.0f), mk3(1.0f), 0.001f, 10000.0f);
   Hit h; h.t = 0.f; h.u = 0.f; h.v = 0.f; h.gid = 0xffffffffu; h.slot = 0;
   int node = WF_DONE, leaf = WF_DONE;
-  auto push = [&](int v) { st.push(v); };
+  auto push = [&](int v, float) { st.push(v); };  // (canonical links, no distance key: pt_device.h trace_closest)
   auto pop = [&]() -> int { return st.sp ? st.pop_nz() : WF_DONE; };
   for (;;) {
     // lanes whose ray finished take the next pending rays of the run, once `refill` of them are

@@ -4,6 +4,9 @@ C3 workload, interleaved rounds in ONE process (cdna_hip_programming.md §5.4 ru
 
   python tools/ab_pt.py base w4 ...     (variant "base" = libptgs.so)
 
+e.g. the walk without the cull at pop: build.build(defines=("PTGS_PT_STACK_CULL=0",), variant="nocull"), then
+`tools/ab_pt.py nocull base`.
+
 AB_SCENE=c5 times C5's mesh instead (the 1M-triangle atrium at 3840x2160, whose tree launches the DEEP
 kernels and whose nodes exceed an XCD's L2); AB_SPP, AB_ROUNDS, AB_CALLS as before. Each variant's image is
 compared with the first variant's first image.
