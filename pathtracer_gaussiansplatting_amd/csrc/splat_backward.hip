@@ -4,9 +4,11 @@
 // the frame that forward published: every tile's depth-sorted Gaussians and the per-Gaussian blend records.
 // Two launches:
 //   1. blend backward   one workgroup per 16x16 tile, one pixel per lane (the forward's quadrant-per-wave
-//                       mapping). The records are staged through LDS in batches of 256 in the forward's
-//                       staged form, so z, the alpha >= 1/255 skip and the T < 1e-4 stop are the forward's
-//                       own expressions. Two front-to-back walks: the first recomputes what the forward
+//                       mapping). The records are staged through LDS in batches of 256; z = A dx^2 + B dx dy +
+//                       C dy^2 + log2 o is evaluated from (dx, dy) = pixel - 2D mean, and the alpha >= 1/255
+//                       skip and the T < 1e-4 stop are the forward's tests on it (the forward's z, the same
+//                       quadratic expanded in tile-local coordinates, differs by its rounding: about 3e-5 of
+//                       alpha). Two front-to-back walks: the first recomputes what the forward
 //                       does not keep (the pixel's T_final and, folded into one number, the whole sum
 //                       dL/dC . C + dL/dT_final T_final); the second walks again with the prefix of that
 //                       sum, which gives each pair's suffix without a division by 1 - alpha per step, and
@@ -58,7 +60,7 @@ __global__ __launch_bounds__(GB_BLOCK) void gs_blend_backward_kernel(uint32_t W,
                                                                       float bg_g, float bg_b,
                                                                       const float4* __restrict__ dout,
                                                                       float* __restrict__ acc) {
-  __shared__ float4 s_stage[3 * GB_BLOCK];  // (A, B, C, D) (E, F, r, g) (b, gx, gy, -): see the forward's stage_rec
+  __shared__ float4 s_stage[3 * GB_BLOCK];  // (A, B, C, L) (-, -, r, g) (b, gx, gy, -): the record, mean tile-local
   __shared__ __attribute__((aligned(16))) float s_red[4][GB_CHUNK * GS_BWD_ACC];  // per wave, per pair of a chunk
   __shared__ uint32_t s_gid[GB_BLOCK];
   __shared__ uint8_t s_mask[GB_BLOCK];
@@ -72,12 +74,17 @@ __global__ __launch_bounds__(GB_BLOCK) void gs_blend_backward_kernel(uint32_t W,
   const uint32_t py = tile_y * GB_TILE + (wave >> 1) * 8u + (lane >> 3);
   const bool inside = px < W && py < H;
   const float4 go = inside ? dout[(size_t)py * W + px] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  const float ux = (float)px - tx0, uy = (float)py - ty0, uxx = ux * ux, uxy = ux * uy, uyy = uy * uy;
+  const float ux = (float)px - tx0, uy = (float)py - ty0;
   // out.rgb = C + T_final bg, out.a = 1 - T_final: dL/dT_final
   const float g_tf = ((go.x * bg_r + go.y * bg_g) + go.z * bg_b) - go.w;
-  float total = 0.0f;  // sum over the pixel's pairs of wgt (c . dL/dC), + T_final dL/dT_final
+  // sum over the pixel's pairs of wgt (c . dL/dC), + T_final dL/dT_final. It and its running prefix are f64
+  // sums of the f32 terms: what lies behind a pair is their difference, and deep in a list (T small) that is
+  // far smaller than either, so the rounding of f32 sums (eps |total|) swamped the gradients of occluded
+  // Gaussians (1.3e-4 relative L2 on the quarter of a case's Gaussians with the smallest opacity gradients)
+  double total = 0.0;
   for (int pass = 0; pass < 2; ++pass) {
-    float T = 1.0f, prefix = 0.0f;
+    float T = 1.0f;
+    double prefix = 0.0;
     bool done = !inside;
     for (uint32_t base = 0; base < n; base += GB_BLOCK) {
       // (every wave is done with the previous batch's records and sums)
@@ -86,12 +93,15 @@ __global__ __launch_bounds__(GB_BLOCK) void gs_blend_backward_kernel(uint32_t W,
       if (idx < n) {
         const uint32_t g = vals[range.x + idx];
         const float4 ga = rec[3 * g], gb = rec[3 * g + 1], gc = rec[3 * g + 2];
-        // the forward's staged quadratic in tile-local pixel coordinates (same expressions: same z)
-        const float gx = ga.x - tx0, gy = ga.y - ty0, A = ga.z, B = ga.w, C = gb.x;
-        const float D = -2.0f * A * gx - B * gy, E = -B * gx - 2.0f * C * gy;
-        const float F = ((A * gx * gx + B * gx * gy) + C * gy * gy) + gb.y;
-        s_stage[3 * tid] = make_float4(A, B, C, D);
-        s_stage[3 * tid + 1] = make_float4(E, F, gb.z, gb.w);
+        // the record's quadratic and the 2D mean in tile-local pixel coordinates. z is evaluated from
+        // (dx, dy) = pixel - mean, as ptgs.h states the function, not from the forward's expansion into
+        // A ux^2 + ... + F: there terms of several hundred cancel to a z of a few units, an error of 3e-5
+        // in alpha that the forward's 1e-4 allowance covers but that reached 1.5e-4 relative L2 in the
+        // gradients of the quarter of a case's Gaussians with the smallest ones (5e-6, float32 autograd's
+        // own error there, in this form)
+        const float gx = ga.x - tx0, gy = ga.y - ty0;
+        s_stage[3 * tid] = make_float4(ga.z, ga.w, gb.x, gb.y);
+        s_stage[3 * tid + 1] = make_float4(0.0f, 0.0f, gb.z, gb.w);
         s_stage[3 * tid + 2] = make_float4(gc.x, gx, gy, 0.0f);
         s_gid[tid] = g;
         // the forward's quadrant mask of the record's alpha box (gc.y, gc.z: the half-extents outside
@@ -120,8 +130,8 @@ __global__ __launch_bounds__(GB_BLOCK) void gs_blend_backward_kernel(uint32_t W,
           const uint32_t k = (uint32_t)__builtin_ctzll(todo), j = c0 + k;
           todo &= todo - 1ull;
           const float4 a = s_stage[3 * j], b = s_stage[3 * j + 1], c = s_stage[3 * j + 2];
-          const float z = __builtin_fmaf(a.x, uxx, __builtin_fmaf(a.y, uxy, __builtin_fmaf(a.z, uyy,
-                                         __builtin_fmaf(a.w, ux, __builtin_fmaf(b.x, uy, b.y)))));
+          const float dx = ux - c.y, dy = uy - c.z;
+          const float z = __builtin_fmaf(a.x * dx, dx, __builtin_fmaf(a.y * dx, dy, __builtin_fmaf(a.z * dy, dy, a.w)));
           bool valid = z >= -7.9943534f && !done;  // alpha >= 1/255
           if (__builtin_amdgcn_ballot_w64(valid) == 0ull) continue;  // no lane of the wave evaluates the pair
           const float e = __builtin_amdgcn_exp2f(z);
@@ -136,16 +146,15 @@ __global__ __launch_bounds__(GB_BLOCK) void gs_blend_backward_kernel(uint32_t W,
           }
           const float cdot = (b.z * go.x + b.w * go.y) + c.x * go.z;
           if (!pass) {
-            total += wgt * cdot;
+            total += (double)(wgt * cdot);
           } else {
-            prefix += wgt * cdot;
+            prefix += (double)(wgt * cdot);
             if (__builtin_amdgcn_ballot_w64(valid) != 0ull) {  // (uniform: every lane takes part in the sums)
               // dL/dalpha = T (c . dL/dC) - (what lies behind the pair) / (1 - alpha); the 0.99 clamp
               // passes nothing to z
-              const float behind = total - prefix;
+              const float behind = (float)(total - prefix);
               const float dalpha = T * cdot - behind / (1.0f - alpha);
               const float dz = (valid && e <= 0.99f) ? dalpha * alpha * GB_LN2 : 0.0f;
-              const float dx = ux - c.y, dy = uy - c.z;
               const float v0 = dz * (-2.0f * a.x * dx - a.y * dy), v1 = dz * (-a.y * dx - 2.0f * a.z * dy);
               const float s0 = gb_wave_sum(v0), s1 = gb_wave_sum(v1);
               const float s2 = gb_wave_sum(dz * dx * dx), s3 = gb_wave_sum(dz * dx * dy), s4 = gb_wave_sum(dz * dy * dy);
@@ -172,7 +181,7 @@ __global__ __launch_bounds__(GB_BLOCK) void gs_blend_backward_kernel(uint32_t W,
         }
       }
     }
-    if (!pass) total += T * g_tf;
+    if (!pass) total += (double)(T * g_tf);
   }
 }
 

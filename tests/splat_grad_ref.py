@@ -21,9 +21,10 @@ BORDER = 1e-3
 GRAD_KEYS = ("colors", "opacities", "means2d", "conics", "means", "scales", "rotations")
 
 
-def make_ubo(W, H):
-    """The identity camera at the origin looking down -Z (synthetic.gaussians_c2's frame), aspect W / H."""
-    pose = Camera(aspect=W / H).look_at([0.0, 0.0, 0.0], [0.0, 0.0, -1.0])
+def make_ubo(W, H, eye=(0.0, 0.0, 0.0), center=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0)):
+    """Camera.look_at(eye, center, up) with aspect W / H; the default is the identity camera at the origin looking
+    down -Z (synthetic.gaussians_c2's frame)."""
+    pose = Camera(aspect=W / H).look_at(list(eye), list(center), list(up))
     u = Ubo()
     u.view[:] = [float(x) for x in pose.view]
     u.proj[:] = [float(x) for x in pose.proj]
@@ -67,10 +68,12 @@ def _project(means, scales, rots, view, proj, W, H):
 
 def evaluate(g, ubo, W, H, bg, frame, dL_dout, dtype=torch.float64):
     """g: dict of float32 numpy arrays; frame: oracle.splat_gaussians(g, ubo, W, H, bg); dL_dout [H, W, 4].
-    Returns {"image" [H, W, 4], "grads" {GRAD_KEYS: numpy float64}, "borderline", "clamped", "stopped"}:
+    Returns {"image" [H, W, 4], "grads" {GRAD_KEYS: numpy float64}, "borderline", "clamped", "stopped", "tiles"}:
     borderline = pairs whose o exp(power) lies within 1e-3 relative of 1/255 or of 0.99 + pixels whose stop
     test lies within 1e-3 relative of 1e-4; clamped = pairs blended at 0.99; stopped = pixels that stop
-    on T < 1e-4."""
+    on T < 1e-4; tiles = per tile {"n": the list's length, "first": per pixel inside the image the position of
+    the entry that stops it (n: none), "quads": per entry the 8x8 quadrants (bit (x >= 8) + 2 (y >= 8)) holding a
+    pixel that evaluates it with alpha >= 1/255}."""
     n = g["means"].shape[0]
     leaf = {k: torch.tensor(np.asarray(g[k], np.float64), dtype=dtype, requires_grad=True)
             for k in ("means", "scales", "rotations", "opacities", "colors")}
@@ -89,6 +92,7 @@ def evaluate(g, ubo, W, H, bg, frame, dL_dout, dtype=torch.float64):
     image = torch.zeros((H, W, 4), dtype=dtype)
     loss = torch.zeros((), dtype=dtype)
     borderline = clamped_n = stopped_n = 0
+    tiles = []
     for t in range(gx_t * gy_t):
         ty_, tx_ = divmod(t, gx_t)
         ys = torch.arange(ty_ * TILE, min(H, (ty_ + 1) * TILE))
@@ -97,6 +101,7 @@ def evaluate(g, ubo, W, H, bg, frame, dL_dout, dtype=torch.float64):
         py, px = py.reshape(-1), px.reshape(-1)
         ids = frame["vals"][ranges[t, 0]:ranges[t, 1]].astype(np.int64)
         npx = px.numel()
+        tiles.append({"n": len(ids), "first": np.zeros(npx, np.int64), "quads": np.zeros(len(ids), np.uint8)})
         if len(ids) == 0:
             rgba = torch.cat([bgt.expand(npx, 3), torch.zeros((npx, 1), dtype=dtype)], 1)
         else:
@@ -124,6 +129,11 @@ def evaluate(g, ubo, W, H, bg, frame, dL_dout, dtype=torch.float64):
             borderline += int((seen & ((keep / 1e-4 - 1.0).abs() < BORDER)).any(1).sum())
             clamped_n += int((active & clamp & ~skip).sum())
             stopped_n += int(stop.any(1).sum())
+            tiles[t]["first"] = first.numpy().copy()
+            quad = ((px % TILE) >= 8).to(torch.int64) + 2 * ((py % TILE) >= 8).to(torch.int64)
+            hit = seen & ~skip
+            for qd in range(4):
+                tiles[t]["quads"] |= (hit[quad == qd].any(0).numpy().astype(np.uint8) << qd)
             alpha = alpha * active.to(dtype)
             one_m = 1.0 - alpha
             Tincl = torch.cumprod(one_m, 1)
@@ -146,7 +156,7 @@ def evaluate(g, ubo, W, H, bg, frame, dL_dout, dtype=torch.float64):
             grads["means2d"][vis] = m2d.grad.double().numpy()
             grads["conics"][vis] = conic.grad.double().numpy()
     return {"image": image.double().numpy(), "grads": grads, "borderline": borderline, "clamped": clamped_n,
-            "stopped": stopped_n}
+            "stopped": stopped_n, "tiles": tiles}
 
 
 def rel_l2(a, b):
@@ -193,17 +203,183 @@ def _case_opaque(seed=14):
     return g, 32, 32
 
 
-CASES = {"edges": _case_edges, "batches": _case_batches, "opaque": _case_opaque}
+# The posed cases: an off-axis eye, a centre off the box axis and a tilted up vector, so that every entry of the
+# view rotation and the translation are non-zero (asserted by the tests). A case that returns a pose is rendered
+# with it; its Gaussians are placed in camera space (pixel, depth) and moved to the world with the inverse view.
+POSE = ((5.0, 2.5, 1.0), (0.3, -0.2, -8.0), (0.4, 1.0, 0.1))
 
 
-def make_case(name):
+def _view_proj(W, H, pose):
+    u = make_ubo(W, H, *pose)
+    return (np.asarray(u.view, np.float64).reshape(4, 4).T, np.asarray(u.proj, np.float64).reshape(4, 4).T)
+
+
+def _cam_to_world(cam_pts, view):
+    inv = np.linalg.inv(view)
+    return np.asarray(cam_pts, np.float64) @ inv[:3, :3].T + inv[:3, 3]
+
+
+def _pixels_to_cam(px, py, d, proj, W, H):
+    """Camera-space points that project to the pixel coordinates (px, py) at view depth d."""
+    px, py, d = (np.asarray(v, np.float64) for v in (px, py, d))
+    return np.stack([((2.0 * px + 1.0) / W - 1.0) * d / proj[0, 0], ((2.0 * py + 1.0) / H - 1.0) * d / proj[1, 1],
+                     -d], -1)
+
+
+def _small_in_tile(rng, n, tile_x, tile_y, W, H, view, proj, opac, depth=(5.0, 9.0), box=(4.5, 10.5),
+                   sigma_px=(0.1, 0.5)):
+    """n small Gaussians whose means fall at tile-local pixels `box` of one tile, so that their 3-sigma rects
+    (radius <= 4 px) touch that tile only; sigma_px: the scales' range in pixels (before the 0.3 dilation)."""
+    px = 16 * tile_x + rng.uniform(box[0], box[1], n)
+    py = 16 * tile_y + rng.uniform(box[0], box[1], n)
+    d = rng.uniform(depth[0], depth[1], n)
+    fx = proj[0, 0] * W * 0.5
+    return {"means": _cam_to_world(_pixels_to_cam(px, py, d, proj, W, H), view),
+            "scales": rng.uniform(sigma_px[0], sigma_px[1], (n, 3)) * (d / fx)[:, None],
+            "rotations": rng.normal(size=(n, 4)),
+            "opacities": rng.uniform(opac[0], opac[1], n),
+            "colors": rng.uniform(0.0, 1.0, (n, 3))}
+
+
+def _concat(parts):
+    return {k: np.concatenate([np.asarray(p[k]) for p in parts], 0) for k in parts[0]}
+
+
+def _case_posed(seed=1):
+    """(e) 44x40 at POSE: partial tiles, the view a general rotation and translation. Gaussian 11 has opacity
+    exactly 0.0 (exactly zero gradients), Gaussian 23 a rotation scaled by 1e-3 (the / |q| path)."""
+    g = Y.gaussians_c2(150, seed=seed)
+    g["scales"] *= 6.0
+    g["opacities"][11] = 0.0
+    g["rotations"][23] *= 1e-3
+    return g, 44, 40, POSE
+
+
+CLAMP_WIDE = 6  # the last Gaussians of the case clamp: 2 beyond the clamp in x only, 2 in y only, 2 in both
+
+
+def _case_clamp(seed=23):
+    """(f) 48x40 at POSE: six Gaussians outside the frustum at |x / d| and / or |y / d| of 1.35 to 1.6 half-angle
+    tangents (the EWA clamp acts at 1.3), wide enough to reach the image."""
+    W, H = 48, 40
+    g = Y.gaussians_c2(80, seed=seed)
+    g["scales"] *= 3.0
+    view, proj = _view_proj(W, H, POSE)
+    rng = np.random.default_rng(5000 + seed)
+    tanx, tany = 1.0 / proj[0, 0], 1.0 / abs(proj[1, 1])
+    d = rng.uniform(5.0, 9.0, CLAMP_WIDE)
+    beyond = rng.uniform(1.35, 1.6, (CLAMP_WIDE, 2)) * rng.choice([-1.0, 1.0], (CLAMP_WIDE, 2))
+    within = rng.uniform(-0.8, 0.8, (CLAMP_WIDE, 2))
+    fx = np.where(np.array([1, 1, 0, 0, 1, 1], bool), beyond[:, 0], within[:, 0])
+    fy = np.where(np.array([0, 0, 1, 1, 1, 1], bool), beyond[:, 1], within[:, 1])
+    cam = np.stack([fx * tanx * d, fy * tany * d, -d], -1)
+    wide = {"means": _cam_to_world(cam, view), "scales": rng.uniform(0.5, 1.2, (CLAMP_WIDE, 3)),
+            "rotations": rng.normal(size=(CLAMP_WIDE, 4)), "opacities": rng.uniform(0.3, 0.9, CLAMP_WIDE),
+            "colors": rng.uniform(0.0, 1.0, (CLAMP_WIDE, 3))}
+    return _concat([g, wide]), W, H, POSE
+
+
+CHUNK_TILES = {(0, 0): 64, (2, 0): 65, (1, 2): 256, (3, 2): 257}  # (tile x, tile y): the list's length
+
+
+def _case_chunks(seed=23):
+    """(g) 60x44 at POSE: four tiles whose lists hold exactly 64, 65, 256 and 257 pairs (the reduction round's
+    and the staged batch's boundaries), small Gaussians of low opacity that touch their own tile only."""
+    W, H = 60, 44
+    view, proj = _view_proj(W, H, POSE)
+    rng = np.random.default_rng(6000 + seed)
+    parts = [_small_in_tile(rng, n, tx, ty, W, H, view, proj, (0.05, 0.35)) for (tx, ty), n in CHUNK_TILES.items()]
+    return _concat(parts), W, H, POSE
+
+
+DEEP_WALK_TILE, DEEP_MIXED_TILE = (0, 0), (2, 1)
+
+
+def _case_deep(seed=48):
+    """(h) 48x32 at POSE: tile (0, 0) holds 530 faint pairs (three batches, pixels that never stop); tile (2, 1)
+    holds 50 layers of opacity 0.8 over one corner in front of 250 faint pairs (pixels that stop inside the
+    first batch next to pixels that walk into the second)."""
+    W, H = 48, 32
+    view, proj = _view_proj(W, H, POSE)
+    rng = np.random.default_rng(7000 + seed)
+    walk = _small_in_tile(rng, 530, *DEEP_WALK_TILE, W, H, view, proj, (0.02, 0.12))
+    front = _small_in_tile(rng, 50, *DEEP_MIXED_TILE, W, H, view, proj, (0.8, 0.8), depth=(3.0, 4.0), box=(4.5, 6.5),
+                           sigma_px=(0.3, 0.6))
+    back = _small_in_tile(rng, 250, *DEEP_MIXED_TILE, W, H, view, proj, (0.05, 0.35))
+    return _concat([walk, front, back]), W, H, POSE
+
+
+def _case_deep_stop(seed=2):
+    """(i) 16x16 at POSE, one tile: 120 layers of opacity 0.8, each wide enough to cover the tile (their alpha
+    1/255 contour lies outside the image), in front of 180 faint pairs: every pixel stops inside the first batch
+    of a list of 300."""
+    W, H = 16, 16
+    view, proj = _view_proj(W, H, POSE)
+    rng = np.random.default_rng(8000 + seed)
+    front = _small_in_tile(rng, 120, 0, 0, W, H, view, proj, (0.8, 0.8), depth=(3.0, 4.0), box=(5.0, 10.0),
+                           sigma_px=(7.0, 9.0))
+    back = _small_in_tile(rng, 180, 0, 0, W, H, view, proj, (0.05, 0.35))
+    return _concat([front, back]), W, H, POSE
+
+
+CASES = {"edges": _case_edges, "batches": _case_batches, "opaque": _case_opaque, "posed": _case_posed,
+         "clamp": _case_clamp, "chunks": _case_chunks, "deep": _case_deep, "deep_stop": _case_deep_stop}
+_DL_SEED = {"batches": 1000, "edges": 1001, "opaque": 1002, "posed": 1003, "clamp": 1004, "chunks": 1005,
+            "deep": 1006, "deep_stop": 1007}
+
+
+def make_case(name, **kw):
     """(g, ubo, W, H, bg, dL_dout): (d) every case has a non-zero background and a seeded random-normal upstream
     gradient on all four channels."""
-    g, W, H = CASES[name]()
+    g, W, H, *pose = CASES[name](**kw)
     g = {k: np.ascontiguousarray(v, np.float32) for k, v in g.items()}
-    rng = np.random.default_rng(1000 + sorted(CASES).index(name))
+    rng = np.random.default_rng(_DL_SEED[name])
     dL = rng.normal(size=(H, W, 4)).astype(np.float32)
-    return g, make_ubo(W, H), W, H, BG, dL
+    return g, make_ubo(W, H, *(pose[0] if pose else ())), W, H, BG, dL
+
+
+def ewa_clamped(g, ubo, frame):
+    """(in x, in y): per Gaussian, visible in the oracle frame and beyond the EWA clamp (|pv.x / d| > 1.3 / P00,
+    |pv.y / d| > 1.3 / |P11|), computed in float64 from the ubo."""
+    view = np.asarray(ubo.view, np.float64).reshape(4, 4).T
+    pv = np.c_[np.asarray(g["means"], np.float64), np.ones(len(g["means"]))] @ view.T
+    d = -pv[:, 2]
+    vis = np.asarray(frame["radii"]) > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cx = np.abs(pv[:, 0] / d) > 1.3 / float(ubo.proj[0])
+        cy = np.abs(pv[:, 1] / d) > 1.3 / abs(float(ubo.proj[5]))
+    return vis & cx, vis & cy
+
+
+def subsets(c, key):
+    """[(label, indices)]: the subsets of Gaussians on which the error bound is checked besides the whole array:
+    each quarter of the visible Gaussians ranked by the norm of their float64 reference gradient in `key` (q1: the
+    smallest), and the Gaussians beyond the EWA clamp where there are any."""
+    ref = c["r64"]["grads"][key]
+    vis = np.flatnonzero(np.asarray(c["frame"]["radii"]) > 0)
+    order = vis[np.argsort(np.linalg.norm(ref[vis].reshape(len(vis), -1), axis=1), kind="stable")]
+    out = [(f"q{i + 1}", part) for i, part in enumerate(np.array_split(order, 4))]
+    cx, cy = ewa_clamped(c["g"], c["ubo"], c["frame"])
+    if (cx | cy).any():
+        out.append(("clamped", np.flatnonzero(cx | cy)))
+    return out
+
+
+def check_bounds(c, key, got, label):
+    """Relative L2 of `got` against the float64 reference in `key`, on the whole array and on every subset,
+    each against max(1e-4, 8 e32) with e32 the float32 reference's error on the same rows. Prints every value;
+    returns the failures."""
+    ref, r32 = c["r64"]["grads"][key], c["r32"]["grads"][key]
+    got = np.asarray(got, np.float64).reshape(ref.shape)
+    failed = []
+    for name, idx in [("all", np.arange(len(ref)))] + subsets(c, key):
+        e32 = rel_l2(r32[idx], ref[idx])
+        bound = max(1e-4, 8.0 * e32)
+        err = rel_l2(got[idx], ref[idx])
+        print(f"{c['name']} {key} {name} ({len(idx)}): {label} rel L2 {err:.2e}  e32 {e32:.2e}  bound {bound:.1e}")
+        if not err <= bound:
+            failed.append((key, name, err, bound))
+    return failed
 
 
 _CACHE = {}
@@ -216,5 +392,5 @@ def case_reference(name, oracle):
         frame = oracle.splat_gaussians(g, ubo, W, H, bg=bg)
         r64 = evaluate(g, ubo, W, H, bg, frame, dL, torch.float64)
         r32 = evaluate(g, ubo, W, H, bg, frame, dL, torch.float32)
-        _CACHE[name] = {"g": g, "ubo": ubo, "W": W, "H": H, "bg": bg, "dL": dL, "frame": frame, "r64": r64, "r32": r32}
+        _CACHE[name] = {"name": name, "g": g, "ubo": ubo, "W": W, "H": H, "bg": bg, "dL": dL, "frame": frame, "r64": r64, "r32": r32}
     return _CACHE[name]
