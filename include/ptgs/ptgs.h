@@ -37,7 +37,8 @@ extern "C" {
                              * 4: PTGS_EBADIDS, PTGS_FLAG_SPLAT_OVERLAP. Added since, without a version
                              * change (new functions only): ptgs_gaussians_sh_colors, ptgs_gaussians_activate,
                              * ptgs_gaussians_permute_sh, ptgs_splat_gaussians_backward (with the struct
-                             * ptgs_gaussian_grads); ptgs_read_gaussian_ply in ptgs_host.h */
+                             * ptgs_gaussian_grads), ptgs_gaussians_sh_colors_backward,
+                             * ptgs_gaussians_activate_backward; ptgs_read_gaussian_ply in ptgs_host.h */
 
 /* ---------------- error codes ---------------- */
 #define PTGS_OK 0
@@ -602,6 +603,37 @@ int ptgs_gaussians_sh_colors(ptgs_ctx* ctx, const float* means, const float* sh,
  * Rotations need no activation: ptgs_gaussians.rotations are un-normalised. */
 int ptgs_gaussians_activate(ptgs_ctx* ctx, const float* log_scales, const float* opacity_logits,
                             uint32_t count, float* scales, float* opacities, void* hip_stream);
+/* Backward of ptgs_gaussians_sh_colors (training on checkpoint-format parameters): given dL_dcolors (3N,
+ * e.g. ptgs_gaussian_grads.colors), dL_dsh (N (sh_degree+1)^2 3, the layout of sh; every element is
+ * overwritten; must not alias sh) and, when dL_dmeans != NULL, the colour's dependence on the mean through the
+ * view direction ADDED to dL_dmeans (3N: pass the ptgs_gaussian_grads.means that the rasterizer's backward just
+ * wrote). means, sh, the degrees and camera_pos are the forward call's. Errors and count == 0 as above (a
+ * null means / sh / camera_pos / dL_dcolors / dL_dsh is PTGS_EINVAL; dL_dmeans may be null).
+ * Numerical contract (f32, no FMA, the derivative of the contract above with the two selects held fixed):
+ *   (x, y, z), len and res are recomputed exactly as in the forward (the same operations in the same order)
+ *   dL_dres[c] = (res + 0.5 < 0) ? 0 : dL_dcolors[c]      (the forward's own test, not the stored colour: a
+ *                                                           stored 0 does not say which side it came from)
+ *   dL_dsh[i][k][c] = f_k * dL_dres[c]   (one multiply), f_k being the factor the forward forms in front of
+ *     sh[k]: C0, -(C1*y), C1*z, -(C1*x), C2[0]*xy, C2[1]*yz, C2[2]*(2*zz - xx - yy), ..., C3[6]*x*(3*xx - yy),
+ *     each evaluated as written there; k >= (active_degree+1)^2: 0. Checkable bit for bit.
+ *   v = dL/d(x, y, z) = sum_c dL_dres[c] * sum_k grad f_k(x, y, z) * sh[k][c]   (the polynomial derivatives)
+ *   dL_dmeans[i] += (v - dir * (dir . v)) / len; a Gaussian at the eye (len == 0) adds nothing.
+ *   The order of the operations inside v is not part of the contract (f32 throughout: about 1e-7 relative).
+ * Each Gaussian's three sums are read, added to and written once by its own work-item: no atomics, so the
+ * result is reproducible from run to run. With dL_dmeans == NULL, active_degree == 0 or sh_degree == 0 the
+ * colour does not depend on the direction: that part is skipped and dL_dmeans is neither read nor written. */
+int ptgs_gaussians_sh_colors_backward(ptgs_ctx* ctx, const float* means, const float* sh, uint32_t count,
+                                      uint32_t sh_degree, uint32_t active_degree, const float camera_pos[3],
+                                      const float* dL_dcolors, float* dL_dsh, float* dL_dmeans, void* hip_stream);
+/* Backward of ptgs_gaussians_activate from the ACTIVATED values (what the forward left: scales 3N, opacities
+ * N): dL_dlog_scales = dL_dscales * scales, dL_dlogits = (dL_dopacities * o) * (1.0f - o); plain f32, no
+ * FMA (checkable bit for bit). In place allowed (dL_dlog_scales == dL_dscales, dL_dlogits == dL_dopacities).
+ * These are the derivatives of exp and of the sigmoid; the forward's expx is an exp to about 1e-7 max(1, |x|)
+ * relative, so they differentiate the function computed to that accuracy, not its polynomial term by term.
+ * PTGS_EINVAL: a null context or pointer; count == 0: PTGS_OK. */
+int ptgs_gaussians_activate_backward(ptgs_ctx* ctx, const float* scales, const float* opacities, uint32_t count,
+                                     const float* dL_dscales, const float* dL_dopacities, float* dL_dlog_scales,
+                                     float* dL_dlogits, void* hip_stream);
 /* out[i] = sh[ids[i]] (rows of (sh_degree+1)^2 * 3 floats): SH rows for a copy made by
  * ptgs_gaussians_sort_spatial. out must not alias sh. A row whose id is >= count is written as zeros
  * (never read out of bounds). */
@@ -643,8 +675,9 @@ int ptgs_gaussians_permute_sh(ptgs_ctx* ctx, const float* sh, uint32_t sh_degree
  * count == 0: PTGS_OK, nothing is launched. PTGS_EINVAL (message in ptgs_last_error, nothing enqueued): a
  * null ctx / g / ubo / bg / dL_dout / grads or a null required array, g->ids != NULL, or no matching
  * published frame (above).
- * Not covered: ptgs_gaussians_sh_colors and ptgs_gaussians_activate (element-wise: chain them from
- * grads.colors / scales / opacities), the `over` composite, tile-row shards. */
+ * ptgs_gaussians_sh_colors_backward and ptgs_gaussians_activate_backward continue the chain from
+ * grads.colors / means / scales / opacities to a checkpoint's SH coefficients, log-scales and logits.
+ * Not covered: gradients with respect to the camera, the `over` composite, tile-row shards. */
 typedef struct ptgs_gaussian_grads {
     float* means;      /* 3N */
     float* scales;     /* 3N, w.r.t. the linear scales */

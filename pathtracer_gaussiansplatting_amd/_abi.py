@@ -217,6 +217,8 @@ SYMBOLS = {
     "ptgs_gaussians_chunk_bounds": (_I, [_P, C.POINTER(Gaussians), _P, _P]),
     "ptgs_gaussians_sh_colors": (_I, [_P, _P, _P, _U, _U, _U, _FP, _P, _P]),
     "ptgs_gaussians_activate": (_I, [_P, _P, _P, _U, _P, _P, _P]),
+    "ptgs_gaussians_sh_colors_backward": (_I, [_P, _P, _P, _U, _U, _U, _FP, _P, _P, _P, _P]),
+    "ptgs_gaussians_activate_backward": (_I, [_P, _P, _P, _U, _P, _P, _P, _P, _P]),
     "ptgs_gaussians_permute_sh": (_I, [_P, _P, _U, _P, _U, _P, _P]),
     "ptgs_splat_gaussians_backward": (_I, [_P, C.POINTER(Gaussians), C.POINTER(Ubo), _U, _U, _FP, _P,
                                            C.POINTER(GaussianGrads), _P]),

@@ -5,15 +5,77 @@ differentiates with ptgs_splat_gaussians_backward (HIP kernels on both sides; th
     loss(img).backward()
 
 scales are linear and opacities in [0, 1] (post-activation), rotations un-normalised (w, x, y, z), colors
-linear RGB: chain the activations and the SH colour in torch. The backward pass consumes the frame its
-forward left in the renderer's workspace, so no other splat call of that renderer may come between the two
-(the backward then raises PtgsError). torch is imported on first use.
+linear RGB. splat_sh() takes a checkpoint's parameters instead (log-scales, opacity logits, SH coefficients: what
+load_gaussian_ply returns and a 3DGS trainer optimises):
+
+    img = autograd.splat_sh(renderer, means, log_scales, rotations, opacity_logits, sh, ubo, W, H,
+                            camera_pos=eye)
+
+Its forward is activate_gaussians, sh_colors and splat_gaussians, its backward splat_gaussians_backward,
+sh_colors_backward and activate_gaussians_backward: nothing is evaluated in torch. The backward pass consumes
+the frame its forward left in the renderer's workspace, so no other splat call of that renderer may come
+between the two (the backward then raises PtgsError). torch is imported on first use.
 """
 from __future__ import annotations
 
 from . import _abi
 
 _FN = None
+_FN_SH = None
+
+
+def _publishing(renderer):
+    if not renderer._publish & _abi.FLAG_SPLAT_PUBLISH:  # the backward needs the published frame
+        renderer._publish |= _abi.FLAG_SPLAT_PUBLISH
+        renderer.set_flags(getattr(renderer, "_flags", 0))
+
+
+def _function_sh():
+    global _FN_SH
+    if _FN_SH is not None:
+        return _FN_SH
+    import torch
+
+    class _SplatSh(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, renderer, ubo, W, H, bg, active_degree, camera_pos, means2d_grad, means, log_scales,
+                    rotations, opacity_logits, sh):
+            means, sh = means.detach().contiguous(), sh.detach().contiguous()
+            scales, opacities = renderer.activate_gaussians(log_scales.detach().contiguous(),
+                                                            opacity_logits.detach().contiguous())
+            colors = renderer.sh_colors(means, sh, camera_pos, active_degree=active_degree)
+            g = {"means": means, "scales": scales, "rotations": rotations.detach().contiguous(),
+                 "opacities": opacities, "colors": colors}
+            _publishing(renderer)
+            out = torch.empty((H, W, 4), dtype=torch.float32, device=means.device)
+            renderer.splat_gaussians(g, ubo, W, H, out, bg=bg, want_stats=True)
+            # kept for the backward: the activated values and the colours (g), and the coefficients
+            ctx.renderer, ctx.ubo, ctx.size, ctx.bg, ctx.g, ctx.sh = renderer, ubo, (W, H), bg, g, sh
+            ctx.active_degree, ctx.camera_pos, ctx.means2d_grad = active_degree, camera_pos, means2d_grad
+            return out
+
+        @staticmethod
+        def backward(ctx, dL_dout):
+            W, H = ctx.size
+            r, g = ctx.renderer, ctx.g
+            need = dict(zip(("means", "log_scales", "rotations", "opacity_logits", "sh"), ctx.needs_input_grad[8:]))
+            gr = r.splat_gaussians_backward(g, ctx.ubo, W, H, dL_dout.contiguous().float(), bg=ctx.bg,
+                                            want_means2d=ctx.means2d_grad is not None)
+            if ctx.means2d_grad is not None:
+                ctx.means2d_grad.copy_(gr["means2d"])
+            d_sh = d_ls = d_lo = None
+            if need["sh"] or need["means"]:  # (the direction part adds into the rasterizer's dL/d means)
+                d_sh, _ = r.sh_colors_backward(g["means"], ctx.sh, ctx.camera_pos, gr["colors"],
+                                               active_degree=ctx.active_degree, dL_dmeans=gr["means"],
+                                               want_means=need["means"])
+            if need["log_scales"] or need["opacity_logits"]:
+                d_ls, d_lo = r.activate_gaussians_backward(g["scales"], g["opacities"], gr["scales"], gr["opacities"],
+                                                           out=(gr["scales"], gr["opacities"]))
+            grads = (gr["means"], d_ls, gr["rotations"], d_lo, d_sh)
+            return (None,) * 8 + tuple(v if n else None for v, n in zip(grads, need.values()))
+
+    _FN_SH = _SplatSh
+    return _FN_SH
 
 
 def _function():
@@ -53,3 +115,21 @@ def splat(renderer, means, scales, rotations, opacities, colors, ubo, W: int, H:
     (float32 device tensors: means [N, 3], scales [N, 3], rotations [N, 4], opacities [N], colors [N, 3])."""
     return _function().apply(renderer, ubo, int(W), int(H), tuple(float(b) for b in bg), means, scales, rotations,
                              opacities, colors)
+
+
+def splat_sh(renderer, means, log_scales, rotations, opacity_logits, sh, ubo, W: int, H: int, bg=(0.0, 0.0, 0.0),
+             active_degree=None, camera_pos=None, means2d_grad=None):
+    """RGBA32F [H, W, 4] of a checkpoint's Gaussians seen from `ubo`, differentiable with respect to the five
+    tensors (float32 device tensors: means [N, 3], log_scales [N, 3], rotations [N, 4], opacity_logits [N],
+    sh [N, (d+1)^2, 3]). active_degree (default d) bands are evaluated; camera_pos (default ubo.camera_pos) is
+    the eye the colours are seen from. means2d_grad: a float32 [N, 2] device tensor that the backward pass
+    fills with dL/d(2D mean), the densification statistic."""
+    import torch
+    cam = tuple(float(v) for v in (ubo.camera_pos if camera_pos is None else camera_pos))[:3]
+    if means2d_grad is not None and (not torch.is_tensor(means2d_grad) or means2d_grad.dtype != torch.float32 or
+                                     tuple(means2d_grad.shape) != (int(means.shape[0]), 2) or
+                                     not means2d_grad.is_cuda):
+        raise _abi.PtgsError("means2d_grad must be a float32 [N, 2] device tensor")
+    return _function_sh().apply(renderer, ubo, int(W), int(H), tuple(float(b) for b in bg),
+                                None if active_degree is None else int(active_degree), cam, means2d_grad, means,
+                                log_scales, rotations, opacity_logits, sh)

@@ -1049,6 +1049,40 @@ int ptgs_gaussians_activate(ptgs_ctx* c, const float* log_scales, const float* o
   return PTGS_OK;
 }
 
+int ptgs_gaussians_sh_colors_backward(ptgs_ctx* c, const float* means, const float* sh, uint32_t count,
+                                      uint32_t sh_degree, uint32_t active_degree, const float camera_pos[3],
+                                      const float* dL_dcolors, float* dL_dsh, float* dL_dmeans, void* stream) {
+  if (!c) return PTGS_EINVAL;
+  if (sh_degree > 3) return fail(c, PTGS_EINVAL, "sh_degree %u above 3", sh_degree);
+  if (active_degree > sh_degree)
+    return fail(c, PTGS_EINVAL, "active_degree %u above the stored sh_degree %u", active_degree, sh_degree);
+  if (count == 0) return PTGS_OK;  // (empty arrays may be null)
+  if (!means || !sh || !camera_pos || !dL_dcolors || !dL_dsh) return fail(c, PTGS_EINVAL, "null argument");
+  if (dL_dsh == sh) return fail(c, PTGS_EINVAL, "dL_dsh must not alias sh");
+  if (!is_device_ptr(dL_dsh)) return fail(c, PTGS_EINVAL, "dL_dsh is not a device pointer");
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipError_t e = splat_sh_colors_backward(means, sh, count, sh_degree, active_degree, camera_pos, dL_dcolors,
+                                                dL_dsh, dL_dmeans, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_sh_colors_backward: %s", hipGetErrorString(e));
+  return PTGS_OK;
+}
+
+int ptgs_gaussians_activate_backward(ptgs_ctx* c, const float* scales, const float* opacities, uint32_t count,
+                                     const float* dL_dscales, const float* dL_dopacities, float* dL_dlog_scales,
+                                     float* dL_dlogits, void* stream) {
+  if (!c) return PTGS_EINVAL;
+  if (count == 0) return PTGS_OK;
+  if (!scales || !opacities || !dL_dscales || !dL_dopacities || !dL_dlog_scales || !dL_dlogits)
+    return fail(c, PTGS_EINVAL, "null argument");
+  if (!is_device_ptr(dL_dlog_scales) || !is_device_ptr(dL_dlogits))
+    return fail(c, PTGS_EINVAL, "dL_dlog_scales / dL_dlogits must be device pointers");
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipError_t e = splat_sh_activate_backward(scales, opacities, count, dL_dscales, dL_dopacities, dL_dlog_scales,
+                                                  dL_dlogits, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_activate_backward: %s", hipGetErrorString(e));
+  return PTGS_OK;
+}
+
 int ptgs_gaussians_permute_sh(ptgs_ctx* c, const float* sh, uint32_t sh_degree, const uint32_t* ids, uint32_t count,
                               float* out, void* stream) {
   if (!c) return PTGS_EINVAL;

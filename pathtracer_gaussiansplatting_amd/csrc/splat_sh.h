@@ -12,6 +12,16 @@ hipError_t splat_sh_colors(const float* means, const float* sh, uint32_t count, 
 // scales = expx(log_scales) (3N), opacities = 1 / (1 + expx(-logits)) (N)
 hipError_t splat_sh_activate(const float* log_scales, const float* logits, uint32_t count, float* scales,
                              float* opacities, hipStream_t s);
+// the backward of splat_sh_colors: dsh (count rows, every element written) = dL/d(sh); dmeans: NULL, or
+// dL/d(mean) is added to it (skipped at sh_degree == 0 or active_degree == 0)
+hipError_t splat_sh_colors_backward(const float* means, const float* sh, uint32_t count, uint32_t sh_degree,
+                                    uint32_t active_degree, const float cam[3], const float* dcolors, float* dsh,
+                                    float* dmeans, hipStream_t s);
+// the backward of splat_sh_activate from the activated values: dlog_scales = dscales * scales (3N),
+// dlogits = (dopacities * o) * (1 - o) (N); an output may alias its upstream gradient
+hipError_t splat_sh_activate_backward(const float* scales, const float* opacities, uint32_t count,
+                                      const float* dscales, const float* dopacities, float* dlog_scales,
+                                      float* dlogits, hipStream_t s);
 // out row i = sh row ids[i] (a row of zeros for ids[i] >= count)
 hipError_t splat_sh_permute(const float* sh, uint32_t sh_degree, const uint32_t* ids, uint32_t count, float* out,
                             hipStream_t s);

@@ -28,9 +28,15 @@
 // length made odd (13 / 27 / 49 dwords): 32 lanes reading coefficient j of 32 consecutive rows then
 // hit 32 different banks. Degree 0 has one coefficient per channel and reads it directly.
 // -DPTGS_SH_ROWWISE builds the row-per-work-item form (no staging) for the A/B of DESIGN.md.
+//
+// Training: gs_sh_colors_backward_kernel and gs_activate_backward_kernel differentiate the two (contracts in
+// ptgs.h). The colour's backward is the same stream with a second wide array going out (dL/d sh, 12 K B per
+// Gaussian): the block is staged in as above, each work-item writes its dL/d sh row over its own LDS row, and
+// the block is stored with lane-contiguous stores. The per-Gaussian math of both directions is in
+// splat_sh_math.h (host / device).
 #include "splat_sh.h"
 
-#include "detmath.h"
+#include "splat_sh_math.h"
 
 namespace ptgs {
 namespace {
@@ -38,50 +44,57 @@ namespace {
 constexpr int SH_WG = 256;  // Gaussians per workgroup (the chunk granule of splat.hip)
 constexpr int SH_BATCH = 4;  // staging loads in flight per work-item
 
-constexpr float SH_C0 = 0.28209479177387814f;
-constexpr float SH_C1 = 0.4886025119029199f;
-__device__ constexpr float SH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                                       -1.0925484305920792f, 0.5462742152960396f};
-__device__ constexpr float SH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f,
-                                       0.3731763325901154f,  -0.4570457994644658f, 1.445305721320277f,
-                                       -0.5900435899266435f};
-
-constexpr int sh_row(int deg) { return 3 * (deg + 1) * (deg + 1); }
-
-// row: the Gaussian's coefficients [k][c]; active <= DEG bands are evaluated
-template <int DEG>
-__device__ __forceinline__ void sh_eval(const float* row, uint32_t active, v3 dir, float* out) {
-  float res[3];
+// Stage the block's nfl floats (rows of R, contiguous at src) into LDS rows of stride S with lane-contiguous
+// loads: float4 plus a dword tail when VEC (src 16-B aligned), dwords otherwise. Nothing at or past src + nfl
+// is read. SH_BATCH loads per work-item are issued before the first is stored, to keep bytes in flight.
+template <uint32_t R, uint32_t S, bool VEC>
+__device__ __forceinline__ void sh_stage_in(float* rows, const float* __restrict__ src, uint32_t nfl, uint32_t t) {
+  auto put = [&](uint32_t f, float v) { rows[f + (f / R) * (S - R)] = v; };
+  uint32_t done = 0;
+  if (VEC) {
+    const uint32_t nv = nfl >> 2;
+    for (uint32_t q0 = t; q0 < nv; q0 += SH_BATCH * SH_WG) {
+      float4 v[SH_BATCH];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) res[c] = SH_C0 * row[c];
-  if (DEG >= 1 && active >= 1) {
-    const float x = dir.x, y = dir.y, z = dir.z;
-    const float w1 = SH_C1 * y, w2 = SH_C1 * z, w3 = SH_C1 * x;
+      for (int j = 0; j < SH_BATCH; ++j)
+        if (q0 + j * SH_WG < nv) v[j] = reinterpret_cast<const float4*>(src)[q0 + j * SH_WG];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) res[c] = res[c] - w1 * row[3 + c] + w2 * row[6 + c] - w3 * row[9 + c];
-    if (DEG >= 2 && active >= 2) {
-      const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-      const float w4 = SH_C2[0] * xy, w5 = SH_C2[1] * yz, w6 = SH_C2[2] * (2.0f * zz - xx - yy);
-      const float w7 = SH_C2[3] * xz, w8 = SH_C2[4] * (xx - yy);
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        res[c] = res[c] + w4 * row[12 + c] + w5 * row[15 + c] + w6 * row[18 + c] + w7 * row[21 + c] +
-                 w8 * row[24 + c];
-      if (DEG >= 3 && active >= 3) {
-        const float w9 = SH_C3[0] * y * (3.0f * xx - yy), w10 = SH_C3[1] * xy * z;
-        const float w11 = SH_C3[2] * y * (4.0f * zz - xx - yy);
-        const float w12 = SH_C3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy);
-        const float w13 = SH_C3[4] * x * (4.0f * zz - xx - yy), w14 = SH_C3[5] * z * (xx - yy);
-        const float w15 = SH_C3[6] * x * (3.0f * xx - yy);
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          res[c] = res[c] + w9 * row[27 + c] + w10 * row[30 + c] + w11 * row[33 + c] + w12 * row[36 + c] +
-                   w13 * row[39 + c] + w14 * row[42 + c] + w15 * row[45 + c];
+      for (int j = 0; j < SH_BATCH; ++j) {
+        const uint32_t q = q0 + j * SH_WG;
+        if (q < nv) {
+          put(4 * q, v[j].x);
+          put(4 * q + 1, v[j].y);
+          put(4 * q + 2, v[j].z);
+          put(4 * q + 3, v[j].w);
+        }
       }
     }
+    done = nv << 2;  // (at most 3 floats are left)
   }
+  for (uint32_t f0 = done + t; f0 < nfl; f0 += SH_BATCH * SH_WG) {
+    float v[SH_BATCH];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) out[c] = fmaxx(res[c] + 0.5f, 0.0f);
+    for (int j = 0; j < SH_BATCH; ++j)
+      if (f0 + j * SH_WG < nfl) v[j] = src[f0 + j * SH_WG];
+#pragma unroll
+    for (int j = 0; j < SH_BATCH; ++j)
+      if (f0 + j * SH_WG < nfl) put(f0 + j * SH_WG, v[j]);
+  }
+}
+
+// The way back: the block's nfl floats from the LDS rows to dst, lane-contiguous float4 stores plus a dword
+// tail when VEC (dst 16-B aligned), dword stores otherwise. Nothing at or past dst + nfl is written.
+template <uint32_t R, uint32_t S, bool VEC>
+__device__ __forceinline__ void sh_stage_out(const float* rows, float* __restrict__ dst, uint32_t nfl, uint32_t t) {
+  auto get = [&](uint32_t f) { return rows[f + (f / R) * (S - R)]; };
+  uint32_t done = 0;
+  if (VEC) {
+    const uint32_t nv = nfl >> 2;
+    for (uint32_t q = t; q < nv; q += SH_WG)
+      reinterpret_cast<float4*>(dst)[q] = make_float4(get(4 * q), get(4 * q + 1), get(4 * q + 2), get(4 * q + 3));
+    done = nv << 2;
+  }
+  for (uint32_t f = done + t; f < nfl; f += SH_WG) dst[f] = get(f);
 }
 
 // One workgroup: Gaussians [256 b, 256 b + 256) ∩ [0, count). VEC: sh is 16-B aligned (a block starts
@@ -101,47 +114,14 @@ __global__ __launch_bounds__(SH_WG) void gs_sh_colors_kernel(const float* __rest
   __shared__ float rows[DEG == 0 ? 1 : SH_WG * S];
   const float* row = DEG == 0 ? src + (size_t)t * R : rows + t * S;
   if (DEG > 0) {
-    const uint32_t nfl = nrows * R;  // the block's floats: nothing at or past src + nfl is read
-    auto put = [&](uint32_t f, float v) { rows[f + (f / R) * (S - R)] = v; };
-    // SH_BATCH loads per work-item are issued before the first is stored, to keep bytes in flight
-    uint32_t done = 0;
-    if (VEC) {
-      const uint32_t nv = nfl >> 2;
-      for (uint32_t q0 = t; q0 < nv; q0 += SH_BATCH * SH_WG) {
-        float4 v[SH_BATCH];
-#pragma unroll
-        for (int j = 0; j < SH_BATCH; ++j)
-          if (q0 + j * SH_WG < nv) v[j] = reinterpret_cast<const float4*>(src)[q0 + j * SH_WG];
-#pragma unroll
-        for (int j = 0; j < SH_BATCH; ++j) {
-          const uint32_t q = q0 + j * SH_WG;
-          if (q < nv) {
-            put(4 * q, v[j].x);
-            put(4 * q + 1, v[j].y);
-            put(4 * q + 2, v[j].z);
-            put(4 * q + 3, v[j].w);
-          }
-        }
-      }
-      done = nv << 2;  // (at most 3 floats are left)
-    }
-    for (uint32_t f0 = done + t; f0 < nfl; f0 += SH_BATCH * SH_WG) {
-      float v[SH_BATCH];
-#pragma unroll
-      for (int j = 0; j < SH_BATCH; ++j)
-        if (f0 + j * SH_WG < nfl) v[j] = src[f0 + j * SH_WG];
-#pragma unroll
-      for (int j = 0; j < SH_BATCH; ++j)
-        if (f0 + j * SH_WG < nfl) put(f0 + j * SH_WG, v[j]);
-    }
+    sh_stage_in<R, S, VEC>(rows, src, nrows * R, t);
     __syncthreads();
   }
 #endif
   if (t >= nrows) return;
   const size_t i3 = (size_t)(first + t) * 3;
-  const v3 d = mk3(means[i3], means[i3 + 1], means[i3 + 2]) - cam;
-  const float len = length3(d);
-  const v3 dir = len > 0.0f ? d / len : mk3(0.0f);
+  float len;
+  const v3 dir = sh_dir(means + i3, cam, &len);
   float rgb[3];
   sh_eval<DEG>(row, active, dir, rgb);
   colors[i3] = rgb[0];
@@ -154,6 +134,61 @@ __global__ __launch_bounds__(256) void gs_activate_kernel(const float* log_scale
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i < (size_t)count * 3) scales[i] = expx(log_scales[i]);
   if (i < count) opacities[i] = 1.0f / (1.0f + expx(-logits[i]));
+}
+
+// The backward of gs_sh_colors_kernel, one workgroup per the same 256 rows: the block of coefficients comes in
+// through LDS as there, each work-item overwrites its own LDS row with its row of dL/d(sh) (sh_backward_one
+// reads the row completely first), and the block goes out with lane-contiguous stores. VIN / VOUT: sh / dsh
+// are 16-B aligned. dmeans: NULL (the direction part is skipped), or dL/d(mean) is added to it, each Gaussian
+// by its own work-item: no atomics.
+template <int DEG, bool VIN, bool VOUT>
+__global__ __launch_bounds__(SH_WG) void gs_sh_colors_backward_kernel(const float* __restrict__ means,
+                                                                     const float* __restrict__ sh, uint32_t count,
+                                                                     uint32_t active, v3 cam,
+                                                                     const float* __restrict__ dcolors,
+                                                                     float* __restrict__ dsh, float* dmeans) {
+  constexpr uint32_t R = sh_row(DEG);  // floats per row
+  constexpr uint32_t S = R | 1u;       // LDS row stride
+  const uint32_t first = blockIdx.x * (uint32_t)SH_WG, t = threadIdx.x;
+  const uint32_t left = count - first, nrows = left < (uint32_t)SH_WG ? left : (uint32_t)SH_WG;
+  const float* src = sh + (size_t)first * R;
+  float* dst = dsh + (size_t)first * R;
+#if defined(PTGS_SH_ROWWISE)
+  const float* row = src + (size_t)t * R;
+  float* drow = dst + (size_t)t * R;
+#else
+  __shared__ float rows[DEG == 0 ? 1 : SH_WG * S];
+  const float* row = DEG == 0 ? src + (size_t)t * R : rows + t * S;
+  float* drow = DEG == 0 ? dst + (size_t)t * R : rows + t * S;
+  if (DEG > 0) {
+    sh_stage_in<R, S, VIN>(rows, src, nrows * R, t);
+    __syncthreads();
+  }
+#endif
+  if (t < nrows) {
+    const size_t i3 = (size_t)(first + t) * 3;
+    float len = 0.0f;
+    v3 dir = mk3(0.0f);
+    if (DEG > 0 && active > 0) dir = sh_dir(means + i3, cam, &len);  // (the DC band does not see the direction)
+    const float dcol[3] = {dcolors[i3], dcolors[i3 + 1], dcolors[i3 + 2]};
+    sh_backward_one<DEG>(row, active, dir, len, dcol, drow, dmeans ? dmeans + i3 : nullptr);
+  }
+#if !defined(PTGS_SH_ROWWISE)
+  if (DEG > 0) {
+    __syncthreads();
+    sh_stage_out<R, S, VOUT>(rows, dst, nrows * R, t);
+  }
+#endif
+}
+
+// no __restrict__: an output may be its upstream gradient (in place)
+__global__ __launch_bounds__(256) void gs_activate_backward_kernel(const float* scales, const float* opacities,
+                                                                  uint32_t count, const float* dscales,
+                                                                  const float* dopacities, float* dlog_scales,
+                                                                  float* dlogits) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < (size_t)count * 3) dlog_scales[i] = sh_dlog_scale(dscales[i], scales[i]);
+  if (i < count) dlogits[i] = sh_dlogit(dopacities[i], opacities[i]);
 }
 
 // one work-item per output float: contiguous writes, reads contiguous within a row
@@ -181,6 +216,29 @@ hipError_t launch_sh(const float* means, const float* sh, uint32_t count, uint32
   return hipGetLastError();
 }
 
+template <int DEG>
+hipError_t launch_sh_backward(const float* means, const float* sh, uint32_t count, uint32_t active, v3 cam,
+                              const float* dcolors, float* dsh, float* dmeans, hipStream_t s) {
+  const uint32_t blocks = (uint32_t)(((uint64_t)count + SH_WG - 1) / SH_WG);
+#define PTGS_SH_BWD(VIN, VOUT)                                                                        \
+  gs_sh_colors_backward_kernel<DEG, VIN, VOUT><<<blocks, SH_WG, 0, s>>>(means, sh, count, active, cam, dcolors, \
+                                                                        dsh, dmeans)
+  const bool vin = ((uintptr_t)sh & 15u) == 0, vout = ((uintptr_t)dsh & 15u) == 0;
+  if constexpr (DEG == 0) {  // (degree 0 stages nothing)
+    PTGS_SH_BWD(false, false);
+  } else if (vin && vout) {
+    PTGS_SH_BWD(true, true);
+  } else if (vin) {
+    PTGS_SH_BWD(true, false);
+  } else if (vout) {
+    PTGS_SH_BWD(false, true);
+  } else {
+    PTGS_SH_BWD(false, false);
+  }
+#undef PTGS_SH_BWD
+  return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t splat_sh_colors(const float* means, const float* sh, uint32_t count, uint32_t sh_degree,
@@ -196,11 +254,36 @@ hipError_t splat_sh_colors(const float* means, const float* sh, uint32_t count, 
   return hipErrorInvalidValue;
 }
 
+hipError_t splat_sh_colors_backward(const float* means, const float* sh, uint32_t count, uint32_t sh_degree,
+                                    uint32_t active_degree, const float cam[3], const float* dcolors, float* dsh,
+                                    float* dmeans, hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  const v3 c = mk3(cam[0], cam[1], cam[2]);
+  if (sh_degree == 0 || active_degree == 0) dmeans = nullptr;  // no direction part: neither read nor written
+  switch (sh_degree) {
+    case 0: return launch_sh_backward<0>(means, sh, count, active_degree, c, dcolors, dsh, dmeans, s);
+    case 1: return launch_sh_backward<1>(means, sh, count, active_degree, c, dcolors, dsh, dmeans, s);
+    case 2: return launch_sh_backward<2>(means, sh, count, active_degree, c, dcolors, dsh, dmeans, s);
+    case 3: return launch_sh_backward<3>(means, sh, count, active_degree, c, dcolors, dsh, dmeans, s);
+  }
+  return hipErrorInvalidValue;
+}
+
 hipError_t splat_sh_activate(const float* log_scales, const float* logits, uint32_t count, float* scales,
                              float* opacities, hipStream_t s) {
   if (count == 0) return hipSuccess;
   const uint32_t blocks = (uint32_t)(((uint64_t)count * 3 + 255) / 256);
   gs_activate_kernel<<<blocks, 256, 0, s>>>(log_scales, logits, count, scales, opacities);
+  return hipGetLastError();
+}
+
+hipError_t splat_sh_activate_backward(const float* scales, const float* opacities, uint32_t count,
+                                      const float* dscales, const float* dopacities, float* dlog_scales,
+                                      float* dlogits, hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  const uint32_t blocks = (uint32_t)(((uint64_t)count * 3 + 255) / 256);
+  gs_activate_backward_kernel<<<blocks, 256, 0, s>>>(scales, opacities, count, dscales, dopacities, dlog_scales,
+                                                     dlogits);
   return hipGetLastError();
 }
 

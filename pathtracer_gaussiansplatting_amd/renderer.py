@@ -372,6 +372,46 @@ class Renderer:
         self._chk(rc, "ptgs_gaussians_activate")
         return sc, op
 
+    def sh_colors_backward(self, means, sh, camera_pos, dL_dcolors, active_degree=None, dL_dmeans=None, stream=None,
+                           want_means: bool = True):
+        """ptgs_gaussians_sh_colors_backward: (dL_dsh, dL_dmeans) of sh_colors(means, sh, camera_pos,
+        active_degree=...) given dL_dcolors [N, 3]. dL_dsh is a new tensor shaped like sh; the colour's
+        dependence on the means (through the view direction) is ADDED to dL_dmeans [N, 3] (a zero tensor is
+        allocated when None) and that tensor is returned: pass the "means" of splat_gaussians_backward.
+        want_means=False skips that part (NULL at the C level) and returns (dL_dsh, None).
+        Stream-ordered; reproducible from run to run (no atomics)."""
+        import torch
+        d = self._sh_degree(sh)
+        n = int(means.shape[0])
+        if not want_means:
+            dL_dmeans = None
+        elif dL_dmeans is None:
+            dL_dmeans = torch.zeros((n, 3), dtype=torch.float32, device=means.device)
+        self._f32(("means", means, n * 3), ("sh", sh, n * (d + 1) ** 2 * 3), ("dL_dcolors", dL_dcolors, n * 3),
+                  *([("dL_dmeans", dL_dmeans, n * 3)] if want_means else []))
+        dL_dsh = torch.empty((n, (d + 1) ** 2, 3), dtype=torch.float32, device=means.device)
+        cam = np.ascontiguousarray(np.asarray(camera_pos, np.float32).reshape(3))
+        rc = self.lib.ptgs_gaussians_sh_colors_backward(self._h, _ptr(means), _ptr(sh), n, d,
+                                                        d if active_degree is None else int(active_degree),
+                                                        _abi.fptr(cam), _ptr(dL_dcolors), _ptr(dL_dsh),
+                                                        _ptr(dL_dmeans) if want_means else None, _stream(stream))
+        self._chk(rc, "ptgs_gaussians_sh_colors_backward")
+        return dL_dsh, dL_dmeans
+
+    def activate_gaussians_backward(self, scales, opacities, dL_dscales, dL_dopacities, out=None, stream=None):
+        """ptgs_gaussians_activate_backward: (dL_dlog_scales, dL_dlogits) from the ACTIVATED scales and
+        opacities (activate_gaussians' outputs) and the gradients with respect to them, as new tensors;
+        out=(dL_dlog_scales, dL_dlogits) writes there instead (the upstream gradients themselves: in place)."""
+        import torch
+        n = int(opacities.shape[0])
+        ds, do = out if out is not None else (torch.empty_like(dL_dscales), torch.empty_like(dL_dopacities))
+        self._f32(("scales", scales, n * 3), ("opacities", opacities, n), ("dL_dscales", dL_dscales, n * 3),
+                  ("dL_dopacities", dL_dopacities, n), ("dL_dlog_scales", ds, n * 3), ("dL_dlogits", do, n))
+        rc = self.lib.ptgs_gaussians_activate_backward(self._h, _ptr(scales), _ptr(opacities), n, _ptr(dL_dscales),
+                                                       _ptr(dL_dopacities), _ptr(ds), _ptr(do), _stream(stream))
+        self._chk(rc, "ptgs_gaussians_activate_backward")
+        return ds, do
+
     def permute_sh(self, sh, ids, stream=None):
         """ptgs_gaussians_permute_sh: sh[ids] as a new tensor: the SH rows of the copy that
         sort_gaussians_spatial returned with these ids."""
