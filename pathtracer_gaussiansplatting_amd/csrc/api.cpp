@@ -751,7 +751,7 @@ static int splat_check_args(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo
 }
 
 // Renders one frame whose arguments passed splat_check_args; PTGS_OK means it was enqueued completely.
-// *report (bit 0: an earlier frame was left incomplete, bit 1: an earlier frame met ids >= count) is about
+// *report (SplatReport: an earlier frame was left incomplete / met ids >= count) is about
 // EARLIER frames of the workspace: the caller turns it into PTGS_EINCOMPLETE / PTGS_EBADIDS (splat_report)
 // once everything it renders is enqueued.
 static int splat_render(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t w, uint32_t h,
@@ -762,10 +762,28 @@ static int splat_render(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ub
   HIPCHK(c, hipSetDevice(c->device));
   float mvp[16];
   mat4_mul(ubo->proj, ubo->view, mvp);
-  hipError_t e = splat_gaussians(c->splat, g, ubo->view, mvp, ubo->proj[0], ubo->proj[5], w, h, bg, depth, under,
-                                 tile_row_begin, tile_row_end, out, stats, (c->flags & PTGS_FLAG_TIME_STAGES) != 0,
-                                 (c->flags & PTGS_FLAG_SPLAT_PUBLISH) != 0, (c->flags & PTGS_FLAG_SPLAT_PUBLISH_TIGHT) != 0,
-                                 (hipStream_t)stream, report, ov, seq);
+  SplatArgs a;
+  a.g = g;
+  a.view = ubo->view;
+  a.mvp = mvp;
+  a.p00 = ubo->proj[0];
+  a.p11 = ubo->proj[5];
+  a.W = w;
+  a.H = h;
+  a.bg = bg;
+  a.depth = depth;
+  a.under = under;
+  a.tile_row_begin = tile_row_begin;
+  a.tile_row_end = tile_row_end;
+  a.out = out;
+  a.stats = stats;
+  a.time_stages = (c->flags & PTGS_FLAG_TIME_STAGES) != 0;
+  a.publish = (c->flags & PTGS_FLAG_SPLAT_PUBLISH) != 0;
+  a.publish_tight = (c->flags & PTGS_FLAG_SPLAT_PUBLISH_TIGHT) != 0;
+  a.stream = (hipStream_t)stream;
+  a.ov = ov;
+  a.seq = seq;
+  hipError_t e = splat_gaussians(c->splat, a, report);
   if (e != hipSuccess) return fail(c, PTGS_EHIP, "splat_gaussians: %s", hipGetErrorString(e));
   return PTGS_OK;
 }
@@ -786,11 +804,11 @@ static int splat_finish(ptgs_ctx* c, int rc, uint32_t report) {
   return splat_report(c, report);
 }
 static int splat_report(ptgs_ctx* c, uint32_t report) {
-  if (report & 2u) {
-    c->pending_report = report & 1u;  // (an incomplete frame too: the next call's PTGS_EINCOMPLETE)
+  if (report & SPLAT_REPORT_BAD_IDS) {
+    c->pending_report = report & SPLAT_REPORT_INCOMPLETE;  // (an incomplete frame too: the next call's PTGS_EINCOMPLETE)
     return fail(c, PTGS_EBADIDS, "an earlier splat frame met ptgs_gaussians.ids entries >= count");
   }
-  if (report & 1u)
+  if (report & SPLAT_REPORT_INCOMPLETE)
     return fail(c, PTGS_EINCOMPLETE, "an earlier splat frame left tiles incomplete (spill pool exhausted; grown)");
   return PTGS_OK;
 }

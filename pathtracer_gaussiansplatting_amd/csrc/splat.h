@@ -35,15 +35,30 @@ struct SplatSeq {
   bool launched;
 };
 
-// view/mvp column-major float[16]; p00 = proj[0][0], p11 = proj[1][1] (negative: Vulkan y-down)
-// depth / under (both null, or both device arrays of W*H): the hybrid "over" composite
-// ov: null, or the front-end stream of an overlapped frame (see SplatOverlap; ignored by three-launch frames)
-hipError_t splat_gaussians(SplatWorkspace* w, const ptgs_gaussians* g, const float* view, const float* mvp, float p00,
-                           float p11, uint32_t W, uint32_t H, const float bg[3], const float* depth,
-                           const float* under, uint32_t tile_row_begin, uint32_t tile_row_end, float* out,
-                           ptgs_splat_stats* stats, bool time_stages, bool publish, bool publish_tight, hipStream_t s,
-                           uint32_t* report,  // report: bit 0 an earlier frame was left incomplete, bit 1 ids >= N
-                           const SplatOverlap* ov = nullptr, SplatSeq* seq = nullptr);
+// One frame's arguments
+struct SplatArgs {
+  const ptgs_gaussians* g;
+  const float *view, *mvp;  // column-major float[16]
+  float p00, p11;           // proj[0][0], proj[1][1] (negative: Vulkan y-down)
+  uint32_t W, H;
+  const float* bg;                          // [3]
+  const float *depth, *under;               // both null, or both device arrays of W*H: the hybrid "over" composite
+  uint32_t tile_row_begin, tile_row_end;
+  float* out;
+  ptgs_splat_stats* stats;                  // null: stream-ordered (no wait)
+  bool time_stages;                         // PTGS_FLAG_TIME_STAGES
+  bool publish;                             // PTGS_FLAG_SPLAT_PUBLISH
+  bool publish_tight;                       // PTGS_FLAG_SPLAT_PUBLISH_TIGHT
+  hipStream_t stream;
+  const SplatOverlap* ov;  // null, or the front-end stream of an overlapped frame (ignored by three-launch frames)
+  SplatSeq* seq;           // null, or the blend ordinal of this call
+};
+// *report: about EARLIER frames of the workspace
+enum SplatReport : uint32_t {
+  SPLAT_REPORT_INCOMPLETE = 1u,  // one was left incomplete (spill pool exhausted; grown by this call)
+  SPLAT_REPORT_BAD_IDS = 2u      // one met ptgs_gaussians.ids entries >= N
+};
+hipError_t splat_gaussians(SplatWorkspace* w, const SplatArgs& a, uint32_t* report);
 hipError_t splat_stage_ms(SplatWorkspace* w, float* out_ms);
 // 3D Morton order of the means: a reordered copy + the original indices (synchronises s)
 hipError_t splat_sort_spatial(const ptgs_gaussians* g, float* means, float* scales, float* rots, float* opac,

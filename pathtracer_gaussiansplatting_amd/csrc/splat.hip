@@ -2,22 +2,30 @@
 //
 // The reference has no Gaussian rasterizer; this restates the published forward
 // pass (Kerbl et al., SIGGRAPH 2023) in the reference's camera conventions (glm::lookAt RH view,
-// Vulkan ZO projection with [1][1] negated, camera.cpp:186-187). Four launches per frame:
+// Vulkan ZO projection with [1][1] negated, camera.cpp:186-187). A frame is a front end that bins
+// (Gaussian, tile) pairs, then a per-tile sort and blend. Two front ends (gs_plan_scap chooses):
+//  three launches (the first frames of a workspace, incoherent orders, tiles above GS_FUSED_MAX_SCAP pairs):
 //   1. count        (band of tile rows x chunk of Gaussians) workgroups: preprocess one Gaussian per
 //                   work-item (frustum cull (d <= 0.2), Sigma = R S^2 R^T, EWA Sigma' = J W Sigma W^T J^T
 //                   (+0.3 low-pass), conic, 3-sigma radius, tile rect, a 48-B blend record), then the
 //                   chunk's pairs into an LDS tile histogram (load-balanced wave expansion)
-//   2. colscan      per 64 tiles: prefix of the histograms over the chunks, tile totals, K (to pinned
-//                   host memory)
+//   2. colscan      per 64 tiles: prefix of the histograms over the chunks, tile totals, large-tile list
 //   3. scatter      same grid as 1: (depth << 32 | gaussian) into each touched tile's segment through
-//                   LDS cursors; tile ranges
-//   4. sort+blend   one workgroup per 16x16 tile: sort by (depth, gaussian) (= the order of a stable
+//                   LDS cursors; tile ranges; K and the frame's other hints to pinned host memory
+//  fused (the default once a frame has published its largest tile): one launch, gs_bin_fused_kernel:
+//                   the same preprocess per 256-Gaussian chunk, the chunk's pairs counted in LDS, one
+//                   returning atomic per touched tile reserves a run of the tile's fixed-capacity row;
+//                   the blend's block (0, 0) publishes the hints
+// then, for both:
+//   sort large      (frames after one with a tile above GS_MID pairs) radix sort of the large tiles
+//   sort+blend      one workgroup per 16x16 tile: sort by (depth, gaussian) (= the order of a stable
 //                   global sort of (tile << 32 | depth) keys), publish keys/values, per-quadrant
-//                   culled front-to-back alpha blend
-// 3 and 4 are enqueued before K is read back (pair buffer sized from the previous frame, re-run on
-// growth), so the host never stalls the GPU. Integer outputs (radii, tiles, keys, values, ranges)
-// are the bit-exact contract with oracle/ptgs_oracle.c; the image is within 1e-4 relative L2
-// (hardware exp2 in the blend).
+//                   culled front-to-back alpha blend; a tile whose pairs the front end could not all
+//                   store is completed through the spill pool (gs_spill_tile)
+// Everything is enqueued before K is read back (buffers sized from earlier frames' hints, re-run on
+// growth when stats are requested), so the host never stalls the GPU. Integer outputs (radii, tiles, keys,
+// values, ranges) are the bit-exact contract with oracle/ptgs_oracle.c; the image is within 1e-4 relative
+// L2 (hardware exp2 in the blend).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -30,27 +38,64 @@
 #include "detmath.h"
 #include "splat.h"
 #include "splat_backward.h"
+#include "splat_plan.h"
 #include "splat_probe.h"
 
 namespace ptgs {
 
-#define GS_BLOCK_X 16
-#define GS_BLOCK_Y 16
-#define GS_BLOCK (GS_BLOCK_X * GS_BLOCK_Y)
+// ---- counter words ---------------------------------------------------------------------------------
+// The kernels and the host talk through four small word arrays. Every slot is named here, with its
+// writer (W) and reader (R); front end = count / scatter or the fused kernel, blend = gs_sort_blend_kernel.
 
-struct SplatCam {
-  float view[16];
-  float mvp[16];  // proj * view
-  float fx, fy;   // P00*W/2, P11*H/2 (fy negative: Vulkan y-down)
-  float tan_fovx, tan_fovy;
-  uint32_t W, H;
-  uint32_t grid_x, grid_y;
-  uint32_t row_begin, row_end;  // tile rows
-  uint32_t cull;                // tile rows restricted and chunk bounds given: PreArgs.cskip is valid
-  uint32_t tight;               // bin by the alpha box (frames without stats / published buffers)
-  uint32_t rowcull;             // tile rows restricted: Gaussians whose radius bound misses them skip the rest
-  float fmax2;                  // max(fx^2, fy^2)
-  float w2;                     // an upper bound of the view rotation's squared spectral norm (1 for lookAt)
+// k_host: the pinned, coherent host mailbox (SplatWorkspace::k_host; the device writes through k_dev).
+// Racy hints: the host reads them without waiting, or after the K event when stats are requested.
+enum GsHostWord : uint32_t {
+  GS_KH_PAIRS = 0,        // the frame's pair count K. W: scatter / fused blend block (0, 0). R: pair buffers, queue size, stats
+  GS_KH_MAX_TILE = 1,     // largest tile (fused: a bound, at least 256). W: same. R: scap, the next sort's shape
+  GS_KH_LARGE_TILES = 2,  // tiles above GS_MID pairs. W: same. R: the next sort's grid
+  GS_KH_RUNS = 4,         // touched (workgroup, tile) runs. W: same. R: the front-end policy, splat_front_end_info
+  GS_KH_OVER_SCAP = 5,    // fused: tiles above their row's capacity (scatter: 0). W: same. R: the stats re-run
+  GS_KH_PUBLISHED_BY = 6, // 1 fused / 2 three launches. W: same. A diagnostic: the host does not read it
+  GS_KH_SPILL_DEMAND = 8, // the previous frame's spill demand (pairs). W: gs_spill_rearm. R: the pool's size
+  GS_KH_INCOMPLETE = 9,   // <- 1: a tile the spill pool could not hold. W: gs_spill_tile. R (exchanged with 0): the next call's report, splat_status
+  GS_KH_BAD_IDS = 10,     // <- 1: an id >= N (PreArgs::bad_ids). W: the preprocess. R (exchanged): the next call's report
+  GS_KH_QUEUED = 11,      // slices the fused front end queued. W: fused blend block (0, 0). R: the helper count
+  GS_KH_MAX_K_FUSED = 12, // the workspace's largest K, fused frames (GS_FZ_MAX_K). W: fused blend block (0, 0). R: the pool's size after a report
+  GS_KH_MAX_K_THREE = 13, // the same for three-launch frames (GS_TOT_MAX_K). W: scatter. R: same
+  GS_KH_WORDS = 16
+};
+
+// fz: device counters of both front ends, the blend and the spill pool (zeroed once; each user re-arms
+// what it leaves nonzero). The queue words are polled by the helpers: a cache line of their own.
+enum GsFzWord : uint32_t {
+  GS_FZ_MAX_TILE = 1,     // largest tile above 256 pairs. W: fused front end (atomicMax). R + re-arm: fused blend block (0, 0)
+  GS_FZ_ABOVE_MID = 4,    // tiles above GS_MID pairs. W: fused front end. R + re-arm: same
+  GS_FZ_OVER_SCAP = 5,    // tiles above scap. W: fused front end. R + re-arm: same
+  GS_FZ_POOL_CURSOR = 8,  // spill pool cursor (pairs). W: gs_spill_tile (atomicAdd). R + re-arm: the next front end (gs_spill_rearm), splat_status
+  GS_FZ_SPILLED = 9,      // tiles completed through the pool, ever. W: gs_spill_tile. R: splat_status
+  GS_FZ_INCOMPLETE = 10,  // tiles the pool could not hold, ever. W: gs_spill_tile. R: splat_status
+  GS_FZ_MAX_DEMAND = 11,  // largest spill demand of a frame. W: gs_spill_rearm. R: splat_status
+  GS_FZ_MAX_K = 13,       // largest K of a fused frame. W + R: fused blend block (0, 0), which hands it to GS_KH_MAX_K_FUSED
+  GS_FZ_COUNTERS = 16,    // the counters above: what splat_status reads back
+  GS_FZ_Q_CLAIMS = 32,    // slice queue: claims. W: helpers (atomicAdd). Re-arm: fused blend block (0, 0)
+  GS_FZ_Q_ENTRIES = 33,   // slice queue: entries. W: owners. R: helpers, the blend (GS_KH_QUEUED). Re-arm: same
+  GS_FZ_Q_OWNERS = 34,    // slice queue: owners that have published. W: owners. R: helpers. Re-arm: same
+  GS_FZ_WORDS = 64
+};
+static_assert(GS_FZ_Q_CLAIMS * 4u % 64u == 0 && GS_FZ_Q_OWNERS / 16u == GS_FZ_Q_CLAIMS / 16u &&
+              GS_FZ_COUNTERS <= GS_FZ_Q_CLAIMS, "the queue words share one cache line with no counter");
+
+// total: the three-launch front end's scalars
+enum GsTotalWord : uint32_t {
+  GS_TOT_PAIRS = 0,     // K. W: scatter block (0, 0)
+  GS_TOT_MAX_TILE = 1,  // largest tile. W: colscan (atomicMax); re-arm: count block (0, 0). R: scatter (GS_KH_MAX_TILE)
+  GS_TOT_MAX_K = 2,     // largest K of a three-launch frame. W + R: scatter, which hands it to GS_KH_MAX_K_THREE
+  GS_TOT_WORDS = 4
+};
+// large_ctr: the three-launch large-tile list
+enum GsLargeWord : uint32_t {
+  GS_LC_COUNT = 0,  // its length. W: colscan (atomicAdd); re-arm: count block (0, 0). R: scatter (GS_KH_LARGE_TILES), gs_sort_large_kernel
+  GS_LC_WORDS = 4
 };
 
 struct DevBuf {
@@ -69,17 +114,14 @@ struct SplatWorkspace {
   DevBuf grad_acc;            // the backward pass's per-Gaussian sums (splat_backward.hip)
   uint32_t sp_cap = 0;        // spill pool capacity (pairs)
   uint32_t incomplete = 0;    // frames reported incomplete (spill pool exhausted) since the last status clear
-  uint32_t spilled_base = 0, incomplete_base = 0;  // device counters fz[9] / fz[10] at the last status clear
+  uint32_t spilled_base = 0, incomplete_base = 0;  // GS_FZ_SPILLED / GS_FZ_INCOMPLETE at the last status clear
   bool ids_error = false;     // a frame met an out-of-range ptgs_gaussians.ids entry
   bool have_hint = false;     // a finished frame has published its largest tile: the fused path can size its rows
   bool hint_recorded = false;
   hipEvent_t hint_event = nullptr;
   bool last_fused = false;    // the last frame ran the fused front end
   uint32_t last_scap = 0;     // and its slot rows' capacity (ptgs_splat_get_tile_rows)
-  uint32_t* k_host = nullptr;  // pinned, coherent [16]: K, largest tile, large tiles, -, touched runs,
-                               // fused overflow, publishing path (1 fused / 2 three), -, spill demand,
-                               // incomplete tile, bad ids, queued front-end slices, largest K (fused),
-                               // largest K (three launches)
+  uint32_t* k_host = nullptr;  // pinned, coherent [GS_KH_WORDS] (GsHostWord)
   uint32_t* k_dev = nullptr;   // its device-side address
   hipEvent_t k_event = nullptr;
   uint32_t last_n = 0, last_k = 0, last_tiles = 0;
@@ -452,14 +494,7 @@ __global__ __launch_bounds__(256) void gs_chunk_cull_kernel(SplatCam cam, const 
 #ifndef GS_COUNT_THREADS
 #define GS_COUNT_THREADS 1024  // the count's workgroup (the scatter keeps GS_BIN_THREADS)
 #endif
-#define GS_MAX_CHUNKS 1024   // colscan: 16 waves x up to 64 chunks each
-#ifndef GS_CHUNK_MIN
-#define GS_CHUNK_MIN 512     // Gaussians per chunk (at least)
-#endif
-#define GS_BAND_TILES 8192   // max tiles per band (LDS: 32 KiB count, 64 KiB scatter); W <= 131072 px
-#define GS_TILE_SLOTS 256    // fixed key slots per tile (= the register-sort limit)
-#define GS_MID 512           // tiles of (256, GS_MID] pairs are sorted inside the blend (rank counting)
-#define GS_MAX_GROUPS 4096   // 64-tile groups (262144 tiles)
+// (GS_MAX_CHUNKS, GS_CHUNK_MIN, GS_BAND_TILES, GS_TILE_SLOTS, GS_MID, GS_MAX_GROUPS: splat_plan.h)
 
 // Inclusive wave64 prefix sum in DPP (row_shr 1/2/4/8 inside rows of 16, then row_bcast 15 / 31
 // across rows): six VALU adds instead of six ds_bpermute round trips.
@@ -517,10 +552,6 @@ template <uint32_t J>
 __device__ __forceinline__ unsigned long long lane_xor64(unsigned long long x, uint32_t lane) {
   return ((unsigned long long)lane_xor<J>((uint32_t)(x >> 32), lane) << 32) | lane_xor<J>((uint32_t)x, lane);
 }
-
-struct BinGrid {
-  uint32_t band_rows, bands, chunks, chunk, grid_x, grid_y, tiles, groups, row0, row1;
-};
 
 __device__ __forceinline__ void gs_band(const BinGrid& bg, uint32_t& ty0, uint32_t& ty1) {
   ty0 = bg.row0 + blockIdx.x * bg.band_rows;
@@ -626,7 +657,6 @@ __device__ __forceinline__ void gs_walk_chunk(const BinGrid& bg, const ushort4* 
 // workgroups are dispatched in index order, so its long-running tiles start first and the kernel's
 // ramp-down runs light tiles only. Any permutation renders the same image: the previous frame's
 // counts (ranges[t].y - .x, whatever path wrote them) only steer the schedule.
-#define GS_ORDER_BUCKETS 256u
 #define GS_ORDER_B 4u  // previous tile counts in flight per work-item (16: 104 VGPRs in the front-end kernels)
 // (order[b] = the tile. Carrying the previous frame's count of the tile in the word, so the blend loads
 // only that much of the key row with the tile, measured slower: C2 0.0594 vs 0.0588 ms)
@@ -745,14 +775,14 @@ __global__ __launch_bounds__(GS_ORDER_THREADS) void gs_tile_order_kernel(const u
 }
 
 // Spill accounting (see gs_spill_tile), run by the first front-end launch's block (0, 0): the previous
-// frame's spill demand (fz[8], the pool cursor its spilled tiles advanced; that frame's blend has
-// finished: stream order) goes to the host (k_host[8], the pool's next size) and the running maximum
-// (fz[11]); the cursor restarts at 0 for this frame's blend.
+// frame's spill demand (GS_FZ_POOL_CURSOR, which its spilled tiles advanced; that frame's blend has
+// finished: stream order) goes to the host (GS_KH_SPILL_DEMAND, the pool's next size) and the running
+// maximum (GS_FZ_MAX_DEMAND); the cursor restarts at 0 for this frame's blend.
 __device__ __forceinline__ void gs_spill_rearm(uint32_t* fz, uint32_t* k_host) {
-  const uint32_t d = fz[8];
-  __atomic_store_n(k_host + 8, d, __ATOMIC_RELAXED);
-  if (d > fz[11]) fz[11] = d;
-  fz[8] = 0;  // (k_host[8] reaches the host with the blend's system fence: no fence here)
+  const uint32_t d = fz[GS_FZ_POOL_CURSOR];
+  __atomic_store_n(k_host + GS_KH_SPILL_DEMAND, d, __ATOMIC_RELAXED);
+  if (d > fz[GS_FZ_MAX_DEMAND]) fz[GS_FZ_MAX_DEMAND] = d;
+  fz[GS_FZ_POOL_CURSOR] = 0;  // (the demand reaches the host with the blend's system fence: no fence here)
 }
 
 // Bounding tile rect (x0, y0, x1, y1) of one front-end workgroup's clipped Gaussian rects, reduced over
@@ -808,8 +838,8 @@ __global__ __launch_bounds__(GS_COUNT_THREADS, 4) void gs_bin_count_kernel(Splat
   const uint32_t nt = (ty1 - ty0) * bg.grid_x;
   for (uint32_t k = threadIdx.x; k < nt; k += GS_COUNT_THREADS) s_hist[k] = 0;
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-    total[1] = 0;  // largest tile (colscan's atomicMax; the scatter hands it to the host)
-    large_ctr[0] = 0;  // large-tile list length (colscan)
+    total[GS_TOT_MAX_TILE] = 0;  // (colscan's atomicMax; the scatter hands it to the host)
+    large_ctr[GS_LC_COUNT] = 0;  // (colscan's list)
     gs_spill_rearm(fz, k_host);
   }
   __syncthreads();
@@ -848,7 +878,7 @@ __global__ __launch_bounds__(GS_COUNT_THREADS, 4) void gs_bin_count_kernel(Splat
   }
   // touched (chunk, tile) entries, the front-end policy's measure of spatial coherence (the fused
   // path would reserve each with an atomic), per workgroup; the scatter's block (0, 0) sums them for
-  // the host (k_host[4])
+  // the host (GS_KH_RUNS)
   for (int off = 32; off > 0; off >>= 1) nz += (uint32_t)__shfl_xor((int)nz, off);
   __shared__ uint32_t s_nz[GS_COUNT_THREADS / 64];
   if ((threadIdx.x & 63u) == 0) s_nz[threadIdx.x >> 6] = nz;
@@ -865,7 +895,7 @@ __global__ __launch_bounds__(GS_COUNT_THREADS, 4) void gs_bin_count_kernel(Splat
 // One 256-work-item block per 64-tile group g: wave w sums chunks [w*cpw, (w+1)*cpw) of the group's
 // 64 tiles (lane = tile: coalesced rows), then rewrites hist[c][t] as the exclusive prefix over c.
 // Outputs per tile (offset inside the group, total), per group its total, atomicMax of the largest
-// tile into total[1], and the tiles of more than `thr` pairs appended to the large-tile list.
+// tile into GS_TOT_MAX_TILE, and the tiles of more than `thr` pairs appended to the large-tile list.
 #ifndef GS_COLSCAN_WAVES
 #define GS_COLSCAN_WAVES 16
 #endif
@@ -932,7 +962,7 @@ __global__ __launch_bounds__(GS_COLSCAN_THREADS) void gs_bin_colscan_kernel(BinG
   const unsigned long long bal = __ballot(big);
   if (bal) {
     uint32_t at = 0;
-    if (lane == 0) at = atomicAdd(large_ctr, (uint32_t)__popcll(bal));
+    if (lane == 0) at = atomicAdd(large_ctr + GS_LC_COUNT, (uint32_t)__popcll(bal));
     at = (uint32_t)__shfl((int)at, 0);
     if (big) large[at + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] = t;
   }
@@ -941,14 +971,14 @@ __global__ __launch_bounds__(GS_COLSCAN_THREADS) void gs_bin_colscan_kernel(BinG
   const uint32_t gsum = __shfl(incl, 63);
   if (lane == 0) {
     group_total[blockIdx.x] = gsum;
-    if (mx) atomicMax(total + 1, mx);
+    if (mx) atomicMax(total + GS_TOT_MAX_TILE, mx);
   }
 }
 
-// K = the sum of the group totals (every block scans them all); block (0, 0) publishes it to total[0]
-// (the blend's check) and, with the largest tile and the large-tile count, to pinned host memory. Pairs are written only when K fits the pair buffer
-// (the host sizes it from the previous K and re-runs scatter + blend after growing it when it did
-// not: see splat_gaussians).
+// K = the sum of the group totals (every block scans them all); block (0, 0) publishes it to GS_TOT_PAIRS
+// and, with the frame's other hints, to pinned host memory (GsHostWord). A pair is written only where it
+// fits the pair buffer (the host sizes it from the previous K and, with stats, re-runs scatter + blend
+// after growing it when it did not: see splat_gaussians).
 __global__ __launch_bounds__(GS_BIN_THREADS) void gs_bin_scatter_kernel(
     BinGrid bg, const ushort4* __restrict__ rects, const float* __restrict__ depths, const uint32_t* __restrict__ ids,
     uint32_t n,
@@ -994,15 +1024,15 @@ __global__ __launch_bounds__(GS_BIN_THREADS) void gs_bin_scatter_kernel(
     for (uint32_t w = 0; w < GS_BIN_THREADS / 64; ++w) nzsum += s_part[w];
   }
   if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
-    total[0] = carry;
-    __atomic_store_n(k_host + 1, total[1], __ATOMIC_RELAXED);      // largest tile (the next sort's LDS size)
-    __atomic_store_n(k_host + 2, large_ctr[0], __ATOMIC_RELAXED);  // large tiles (the next sort grid)
-    __atomic_store_n(k_host + 4, nzsum, __ATOMIC_RELAXED);         // touched (chunk, tile) entries
-    __atomic_store_n(k_host + 5, 0u, __ATOMIC_RELAXED);
-    __atomic_store_n(k_host + 6, 2u, __ATOMIC_RELAXED);  // published by: three launches
-    __atomic_store_n(k_host, carry, __ATOMIC_RELAXED);  // pinned host word: the host's K read-back
-    if (carry > total[2]) total[2] = carry;  // the workspace's largest K (three launches; fused: fz[13])
-    __atomic_store_n(k_host + 13, total[2], __ATOMIC_RELAXED);
+    total[GS_TOT_PAIRS] = carry;
+    __atomic_store_n(k_host + GS_KH_MAX_TILE, total[GS_TOT_MAX_TILE], __ATOMIC_RELAXED);  // (the next sort's LDS size)
+    __atomic_store_n(k_host + GS_KH_LARGE_TILES, large_ctr[GS_LC_COUNT], __ATOMIC_RELAXED);  // (the next sort grid)
+    __atomic_store_n(k_host + GS_KH_RUNS, nzsum, __ATOMIC_RELAXED);  // touched (chunk, tile) entries
+    __atomic_store_n(k_host + GS_KH_OVER_SCAP, 0u, __ATOMIC_RELAXED);
+    __atomic_store_n(k_host + GS_KH_PUBLISHED_BY, 2u, __ATOMIC_RELAXED);  // three launches
+    __atomic_store_n(k_host + GS_KH_PAIRS, carry, __ATOMIC_RELAXED);  // the host's K read-back
+    if (carry > total[GS_TOT_MAX_K]) total[GS_TOT_MAX_K] = carry;  // (fused frames: GS_FZ_MAX_K)
+    __atomic_store_n(k_host + GS_KH_MAX_K_THREE, total[GS_TOT_MAX_K], __ATOMIC_RELAXED);
     __threadfence_system();  // visible to the host before the kernel ends (the K event has no system fence)
   }
   if (blockIdx.x == 0 && blockIdx.y == 0 && (bg.row0 > 0 || bg.row1 < bg.grid_y)) {
@@ -1067,51 +1097,23 @@ __global__ __launch_bounds__(GS_BIN_THREADS) void gs_bin_scatter_kernel(
 // A tile whose count exceeds scap keeps its first scap keys only: the blend renders it through
 // gs_spill_tile (its pairs gathered again from the per-Gaussian rects / depths band 0 stores here and
 // the per-workgroup chunk rects), so the frame is complete; the next frame sizes its rows from it.
-// fz: [1] largest tile above 256, [4] tiles above GS_MID pairs, [5] tiles above scap; per workgroup
-// fzp: (pairs, reservations); published to the host by the blend's block (0, 0).
-#ifndef GS_FUSED_OWN_CULL
-// a tile-row frame of at most this many chunks: the fused workgroups test their own chunk's bound (no
-// cull launch: C2 bands 1-2 us faster); above it the flags of a cull launch (each workgroup's bound
-// test adds its latency to every round of workgroups: 10M at 4K, band 0 2.26 vs 2.09 ms)
-#define GS_FUSED_OWN_CULL 1024u
-#endif
-#ifndef GS_FUSED_THREADS
-#define GS_FUSED_THREADS 256  // Gaussians per fused workgroup (512 / 1 024 work-items: 1.5 us slower at C2)
-#endif
+// Counters: fz (GS_FZ_MAX_TILE, GS_FZ_ABOVE_MID, GS_FZ_OVER_SCAP) and per workgroup fzp: (pairs,
+// reservations); published to the host by the blend's block (0, 0).
+// (GS_FUSED_OWN_CULL, GS_FUSED_THREADS, GS_FUSED_WG, GS_FUSED_WG_OV, GsFusedShape: splat_plan.h)
 struct GsFused {  // the sort's and the blend's view of a fused-front-end frame (scap == 0: three-launch path)
   uint32_t scap;
   uint32_t* cursor;   // per-tile pair counts (zeroed again by the blend)
-  uint32_t* fz;       // counters (see above)
-  uint32_t* k_host;   // pinned host words (published by blend block (0, 0))
+  uint32_t* fz;       // counters (GsFzWord)
+  uint32_t* k_host;   // pinned host words (GsHostWord; published by blend block (0, 0))
   uint2* ranges;      // the tile ranges the blend writes (t * scap, t * scap + n)
   uint32_t* fzp;      // per front-end workgroup: (pairs, reservations)
   uint32_t nwg;
   const uint32_t* order;  // blend workgroup -> tile (heavy tiles first; null: row-major)
-  uint2* fsq;             // the front end's slice queue (re-armed by block (0, 0): entries and fz[12..14])
+  uint2* fsq;             // the front end's slice queue (re-armed by block (0, 0): entries and GS_FZ_Q_*)
   uint32_t fsq_cap;
   unsigned long long* seq_flag;  // frames in flight: the blend's first workgroup stores `seq` here (SplatSeq)
   unsigned long long seq;
 };
-// Work-items per fused workgroup (GS_FUSED_THREADS Gaussians; all walk the pairs): 512 for a frame on the
-// caller's stream; 256 for an overlapped frame (SplatOverlap), whose front end runs beside the previous
-// frame's blend: a 256-work-item workgroup of at most 64 VGPRs and ~14 KB of LDS takes the slot of one
-// retiring blend workgroup (256 work-items, 64 VGPRs, 17 KB), where a 512-work-item one waited for the
-// blend's tail (measured: the whole front end ran after the blend; C2 frames 63 vs 56 us serial).
-#define GS_FUSED_WG 512
-#ifndef GS_FUSED_WG_OV
-#define GS_FUSED_WG_OV 256
-#endif
-template <uint32_t WG> struct GsFusedShape;
-template <> struct GsFusedShape<512> {
-  static constexpr uint32_t slice = 4096u;  // pairs per slice (C2's chunks hold 1.6k on average, 3.3k at most: one slice)
-  static constexpr uint32_t lds_cap = 0u;   // histogram window in tiles (0: the band's)
-};
-template <> struct GsFusedShape<256> {
-  static constexpr uint32_t slice = 2048u;
-  static constexpr uint32_t lds_cap = 2048u;  // 8 KB (+ 5.6 KB static): within one blend workgroup's LDS
-};
-static_assert(GsFusedShape<256>::lds_cap == 2048u,
-              "tests/test_splat_windows_gpu.py picks its frame sizes around this window (WINDOW): change both");
 
 // The count walk of one slice [p0, p1) of a chunk's pairs (at most GS_FUSED_QREG per work-item): the
 // chunk's rects (s_e: x0 | w << 16, y0 | h << 16, key index, depth bits) and the inclusive scan of
@@ -1183,14 +1185,10 @@ __device__ __forceinline__ uint32_t gs_wg_count_keep(const uint32_t* s_incl, con
 // kernel's length alone. After its slice 0 an owner claims its own still-queued slices (it never
 // waits), so no slice depends on a helper: a helper waits only for owners that have not published yet
 // (owners precede helpers in dispatch order), and gives up after ~100 us (a slice it would have taken
-// is then its owner's). Queue words: fz[GS_FSQ_W] claims (helpers), fz[GS_FSQ_W + 1] entries,
-// fz[GS_FSQ_W + 2] owners done;
+// is then its owner's). Queue words: GS_FZ_Q_CLAIMS (helpers), GS_FZ_Q_ENTRIES, GS_FZ_Q_OWNERS (done);
 // entries are 0 (not written), owner + 1 (open), GS_FSQ_TAKEN; the blend's block (0, 0) re-arms them.
-#ifndef GS_FUSED_HELPERS
-#define GS_FUSED_HELPERS 128u  // helper workgroups per band (one queued slice each)
-#endif
+// (GS_FUSED_HELPERS, helper workgroups per band, one queued slice each: splat_plan.h)
 #define GS_FSQ_TAKEN 0xFFFFFFFFu
-#define GS_FSQ_W 32  // the queue words' offset in fz: a cache line of their own (helpers poll them)
 // waves per SIMD: 512 work-items 6 (3 workgroups per CU; 8 forced SGPR spills), 256 work-items 8 (64 VGPRs)
 #define GS_FUSED_WAVES(WG) ((WG) == 512 ? 6 : 8)
 static_assert(GsFusedShape<512>::slice <= 512u * GS_FUSED_QREG && GsFusedShape<256>::slice <= 256u * GS_FUSED_QREG,
@@ -1249,7 +1247,7 @@ __global__ __launch_bounds__(WG, GS_FUSED_WAVES(WG)) void gs_bin_fused_kernel(Sp
         // with tens of millions of Gaussians
         uint32_t job = 0xFFFFFFFFu, jslice = 0, hidx = 0, spins = 0;
         for (;;) {
-          if (!hidx) hidx = atomicAdd(fz + GS_FSQ_W, 1u) + 1u;  // (1-based: 0 = none claimed)
+          if (!hidx) hidx = atomicAdd(fz + GS_FZ_Q_CLAIMS, 1u) + 1u;  // (1-based: 0 = none claimed)
           const uint32_t idx = hidx - 1u;
           if (idx >= fsq_cap) break;
           // (the entry as one 64-bit word: owner + 1 and slice arrive together, no fence needed)
@@ -1257,8 +1255,8 @@ __global__ __launch_bounds__(WG, GS_FUSED_WAVES(WG)) void gs_bin_fused_kernel(Sp
                                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           const uint32_t v = (uint32_t)ev;
           if (v == 0u) {  // not written yet: done when every owner has published and this index is past the end
-            const uint32_t done = __hip_atomic_load(fz + GS_FSQ_W + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t tail = __hip_atomic_load(fz + GS_FSQ_W + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t done = __hip_atomic_load(fz + GS_FZ_Q_OWNERS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t tail = __hip_atomic_load(fz + GS_FZ_Q_ENTRIES, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if ((done >= nown && idx >= tail) || ++spins > 200u) break;
             // (a few hundred helpers polling: every ~3 us, or their loads crowd out the owners' memory
             // traffic; measured 3x slower owner phases at ~0.05 us per poll)
@@ -1307,7 +1305,7 @@ __global__ __launch_bounds__(WG, GS_FUSED_WAVES(WG)) void gs_bin_fused_kernel(Sp
       if (own && store) gs_store_skipped(A, i);
       if (threadIdx.x == 0) {
         crect[wg] = make_ushort4(1, 1, 0, 0);
-        atomicAdd(fz + GS_FSQ_W + 2, 1u);
+        atomicAdd(fz + GS_FZ_Q_OWNERS, 1u);
         fzp[2 * wg] = 0;
         fzp[2 * wg + 1] = 0;
       }
@@ -1377,7 +1375,7 @@ __global__ __launch_bounds__(WG, GS_FUSED_WAVES(WG)) void gs_bin_fused_kernel(Sp
         // slices 1.. go to the queue (none fit: the owner walks them all itself)
         uint32_t qb = 0xFFFFFFFFu;
         if (nsl > 1u) {
-          qb = atomicAdd(fz + GS_FSQ_W + 1, nsl - 1u);
+          qb = atomicAdd(fz + GS_FZ_Q_ENTRIES, nsl - 1u);
           if (qb + (nsl - 1u) > fsq_cap) {  // (the part inside the queue is marked taken: helpers skip it)
             for (uint32_t k = qb; k < fsq_cap && k < qb + (nsl - 1u); ++k)
               __hip_atomic_store(reinterpret_cast<unsigned long long*>(fsq + k), (unsigned long long)GS_FSQ_TAKEN,
@@ -1392,7 +1390,7 @@ __global__ __launch_bounds__(WG, GS_FUSED_WAVES(WG)) void gs_bin_fused_kernel(Sp
         // published (helpers stop waiting once every owner has; no release fence: an agent-scope one
         // writes back the XCD's L2. A helper that sees every owner done before it sees its entry keeps
         // waiting while its index is below the tail; one that leaves early leaves the slice to its owner)
-        atomicAdd(fz + GS_FSQ_W + 2, 1u);
+        atomicAdd(fz + GS_FZ_Q_OWNERS, 1u);
         s_job[1] = qb;
       }
     }
@@ -1435,10 +1433,10 @@ __global__ __launch_bounds__(WG, GS_FUSED_WAVES(WG)) void gs_bin_fused_kernel(Sp
           s_hist[k0 + j * WG] = base[j];
           acc_pairs += c[j];
           ++acc_res;
-          if (base[j] <= scap && base[j] + c[j] > scap) atomicAdd(fz + 5, 1u);  // (one crossing per spilled tile)
+          if (base[j] <= scap && base[j] + c[j] > scap) atomicAdd(fz + GS_FZ_OVER_SCAP, 1u);  // (one crossing per spilled tile)
           if (base[j] + c[j] > 256u) {
-            atomicMax(fz + 1, base[j] + c[j]);
-            if (base[j] <= GS_MID && base[j] + c[j] > GS_MID) atomicAdd(fz + 4, 1u);  // (one crossing per tile)
+            atomicMax(fz + GS_FZ_MAX_TILE, base[j] + c[j]);
+            if (base[j] <= GS_MID && base[j] + c[j] > GS_MID) atomicAdd(fz + GS_FZ_ABOVE_MID, 1u);  // (one crossing per tile)
           }
         }
       }
@@ -1549,12 +1547,7 @@ __device__ __forceinline__ void bitonic_flip_sort(uint32_t n, Swap swap_if) {
 //  publish  keys_out = tile << 32 | depth, vals_out = gaussian (the blend streams these)
 // A 16-byte-per-comparator LDS bitonic network measured ~5 MB of LDS traffic per 2.6k-pair tile
 // (LDS-bandwidth bound: ~130 us of the 1M-Gaussian frame); the radix moves ~0.2 MB.
-#ifndef GS_SORT_THREADS
-#define GS_SORT_THREADS 256
-#endif
-#ifndef GS_RADIX_MAXR
-#define GS_RADIX_MAXR (8448 / GS_SORT_THREADS)  // items per work-item in LDS: up to 8448 keys
-#endif
+// (GS_SORT_THREADS, GS_RADIX_MAXR: splat_plan.h)
 #define GS_RADIX_MAXN 65535u  // u16 positions: global bitonic above (never met by the configs)
 
 __host__ __device__ constexpr size_t gs_radix_lds(uint32_t rmax) {
@@ -1761,7 +1754,7 @@ __global__ __launch_bounds__(GS_SORT_THREADS) void gs_sort_large_kernel(
     __syncthreads();
     count = s_list[GS_SORT_THREADS];
   } else {
-    count = large_ctr[0];
+    count = large_ctr[GS_LC_COUNT];
   }
   // static striding over the list (a shared work counter serialises: ~30 ns per contended atomic,
   // 210 us for the 1M-Gaussian frame's 7k claims)
@@ -1891,12 +1884,13 @@ struct GStage {  // one staged blend record (see gs_preprocess_one)
 // front ends' keys) collected; then sorted (bitonic: in the LDS arena up to GS_SPILL_LDS keys, else in
 // the pool) and the sorted gaussians written to the spill pool, from which the blend streams them like
 // a large tile's. Same keys, same order, same blend: the image equals a frame whose rows had fit (and
-// the oracle's). The pool (cap pairs per workspace) is reserved per tile with one atomic (fz[8], re-armed
-// by the next frame's front end, which also hands the demand to the host to size the pool); a tile that
-// does not fit is left at the background and counted (fz[10]; k_host[9] = 1: the next call reports it).
+// the oracle's). The pool (cap pairs per workspace) is reserved per tile with one atomic (GS_FZ_POOL_CURSOR,
+// re-armed by the next frame's front end, which also hands the demand to the host to size the pool); a tile
+// that does not fit is left at the background and counted (GS_FZ_INCOMPLETE; GS_KH_INCOMPLETE <- 1: the next
+// call reports it).
 struct GsSpill {
-  uint32_t* fz;                   // device counters: [8] pool cursor, [9] spilled tiles, [10] incomplete tiles
-  uint32_t* k_host;               // pinned host words: [9] <- 1 when a tile could not be completed
+  uint32_t* fz;                   // device counters: GS_FZ_POOL_CURSOR, GS_FZ_SPILLED, GS_FZ_INCOMPLETE
+  uint32_t* k_host;               // pinned host words: GS_KH_INCOMPLETE
   unsigned long long* keys;       // pool: keys of tiles above GS_SPILL_LDS pairs
   uint32_t* vals;                 // pool: sorted gaussians of every spilled tile
   uint32_t cap;                   // pool capacity (pairs)
@@ -1921,12 +1915,12 @@ __device__ const uint32_t* gs_spill_tile(const GsSpill& sp, uint32_t tx, uint32_
   if (tid == 0) {
     s_w[0] = 0;
     s_w[2] = 0;
-    uint32_t off = atomicAdd(sp.fz + 8, n);
-    atomicAdd(sp.fz + 9, 1u);
+    uint32_t off = atomicAdd(sp.fz + GS_FZ_POOL_CURSOR, n);
+    atomicAdd(sp.fz + GS_FZ_SPILLED, 1u);
     if (off > sp.cap || n > sp.cap - off) {
       off = 0xFFFFFFFFu;
-      atomicAdd(sp.fz + 10, 1u);
-      __atomic_store_n(sp.k_host + 9, 1u, __ATOMIC_RELAXED);
+      atomicAdd(sp.fz + GS_FZ_INCOMPLETE, 1u);
+      __atomic_store_n(sp.k_host + GS_KH_INCOMPLETE, 1u, __ATOMIC_RELAXED);
       __threadfence_system();
     }
     s_w[1] = off;
@@ -2071,28 +2065,28 @@ __global__ __launch_bounds__(GS_BLOCK, GS_BLEND_MIN_BLOCKS) void gs_sort_blend_k
       __syncthreads();
     }
     if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
-      const uint32_t big = fu.fz[1];
-      __atomic_store_n(fu.k_host + 1, big > 256u ? big : 256u, __ATOMIC_RELAXED);  // largest tile (bound)
-      __atomic_store_n(fu.k_host + 2, fu.fz[4], __ATOMIC_RELAXED);                  // large tiles
-      __atomic_store_n(fu.k_host + 4, fr, __ATOMIC_RELAXED);                        // reservations
-      __atomic_store_n(fu.k_host + 5, fu.fz[5], __ATOMIC_RELAXED);                  // tiles above scap (spilled)
-      __atomic_store_n(fu.k_host + 6, 1u, __ATOMIC_RELAXED);                       // published by: fused
-      __atomic_store_n(fu.k_host, fp, __ATOMIC_RELAXED);
-      if (fp > fu.fz[13]) fu.fz[13] = fp;  // the workspace's largest K (fused; three launches: total[2])
-      __atomic_store_n(fu.k_host + 12, fu.fz[13], __ATOMIC_RELAXED);
-      fu.fz[1] = 0;
-      fu.fz[4] = 0;
-      fu.fz[5] = 0;
+      const uint32_t big = fu.fz[GS_FZ_MAX_TILE];
+      __atomic_store_n(fu.k_host + GS_KH_MAX_TILE, big > 256u ? big : 256u, __ATOMIC_RELAXED);  // (a bound)
+      __atomic_store_n(fu.k_host + GS_KH_LARGE_TILES, fu.fz[GS_FZ_ABOVE_MID], __ATOMIC_RELAXED);
+      __atomic_store_n(fu.k_host + GS_KH_RUNS, fr, __ATOMIC_RELAXED);  // reservations
+      __atomic_store_n(fu.k_host + GS_KH_OVER_SCAP, fu.fz[GS_FZ_OVER_SCAP], __ATOMIC_RELAXED);  // (spilled)
+      __atomic_store_n(fu.k_host + GS_KH_PUBLISHED_BY, 1u, __ATOMIC_RELAXED);  // fused
+      __atomic_store_n(fu.k_host + GS_KH_PAIRS, fp, __ATOMIC_RELAXED);
+      if (fp > fu.fz[GS_FZ_MAX_K]) fu.fz[GS_FZ_MAX_K] = fp;  // (three-launch frames: GS_TOT_MAX_K)
+      __atomic_store_n(fu.k_host + GS_KH_MAX_K_FUSED, fu.fz[GS_FZ_MAX_K], __ATOMIC_RELAXED);
+      fu.fz[GS_FZ_MAX_TILE] = 0;
+      fu.fz[GS_FZ_ABOVE_MID] = 0;
+      fu.fz[GS_FZ_OVER_SCAP] = 0;
       __threadfence_system();
     }
     if (blockIdx.x == 0 && blockIdx.y == 0) {  // the slice queue of the front end back to empty
-      const uint32_t used = min(fu.fz[GS_FSQ_W + 1], fu.fsq_cap);
+      const uint32_t used = min(fu.fz[GS_FZ_Q_ENTRIES], fu.fsq_cap);
       for (uint32_t k = tid; k < used; k += GS_BLOCK) fu.fsq[k] = make_uint2(0u, 0u);
       if (tid == 0) {
-        __atomic_store_n(fu.k_host + 11, fu.fz[GS_FSQ_W + 1], __ATOMIC_RELAXED);  // queued slices (helpers)
-        fu.fz[GS_FSQ_W] = 0;
-        fu.fz[GS_FSQ_W + 1] = 0;
-        fu.fz[GS_FSQ_W + 2] = 0;
+        __atomic_store_n(fu.k_host + GS_KH_QUEUED, fu.fz[GS_FZ_Q_ENTRIES], __ATOMIC_RELAXED);  // (the helper count)
+        fu.fz[GS_FZ_Q_CLAIMS] = 0;
+        fu.fz[GS_FZ_Q_ENTRIES] = 0;
+        fu.fz[GS_FZ_Q_OWNERS] = 0;
       }
     }
   }
@@ -2476,50 +2470,68 @@ __global__ __launch_bounds__(256) void gs_publish_copy_kernel(const uint2* __res
   }
 }
 
-hipError_t splat_gaussians(SplatWorkspace* w, const ptgs_gaussians* g, const float* view, const float* mvp, float p00,
-                           float p11, uint32_t W, uint32_t H, const float bg[3], const float* depth,
-                           const float* under, uint32_t tile_row_begin, uint32_t tile_row_end, float* out,
-                           ptgs_splat_stats* stats, bool time_stages, bool publish, bool publish_tight, hipStream_t s,
-                           uint32_t* report, const SplatOverlap* ov, SplatSeq* seq) {
+// ---- the frame call --------------------------------------------------------------------------------
+// splat_gaussians is a sequence of stages over one GsCall. The mailbox words (GsHostWord) are racy hints:
+// each stage reads the ones it needs where it runs (some again after the K event, on purpose), never a
+// snapshot taken once per call; the rules applied to them are splat_plan.h's.
+struct GsCall {
+  SplatWorkspace* w;
+  const SplatArgs* a;
+  hipStream_t s;
+  const SplatOverlap* ov;  // null: a serial frame (frames with stats, published or timed always are)
+  uint32_t n, tiles, rows, slot_keys;
+  SplatCam cam;
+  BinGrid bgrid;
+  size_t band_lds;     // a band's histogram (bytes)
+  PreArgs pa;
+  uint32_t nwg_fused;  // the fused front end's owner workgroups (bands x 256-Gaussian chunks)
+  uint32_t* order;     // the blend's tile order (heaviest tiles of the previous frame first; null: no rows)
+  uint32_t scap;       // the fused rows' capacity (0: three launches)
+};
+
+static hipError_t gs_mark(const GsCall& c, int k) {
+  return c.a->time_stages ? hipEventRecord(c.w->ev[k], c.s) : hipSuccess;
+}
+
+// a small word array, allocated and zeroed once
+static hipError_t ensure_zeroed_once(DevBuf& b, uint32_t words) {
+  if (b.p) return hipSuccess;
   hipError_t e;
-  *report = 0;
-  w->last_full = false;  // (a call that fails leaves no frame for the backward pass)
-  if (stats || publish || time_stages) ov = nullptr;  // (these frames are synchronous or instrumented: serial)
-  if (time_stages && !w->ev[0])
+  if ((e = ensure(b, words * 4u))) return e;
+  return hipMemset(b.p, 0, words * 4u);
+}
+
+// The pair capacity the buffers give (the published keys count only for a frame that publishes them)
+static uint32_t pair_capacity(const SplatWorkspace* w, bool publish) {
+  size_t c = std::min(w->pairs.bytes / 8, w->vals_out.bytes / 4);
+  if (publish) c = std::min(c, w->keys_out.bytes / 8);
+  return (uint32_t)std::min<size_t>(c, 0xFFFFFFFFu);
+}
+// Grow the pair buffers to K pairs (hipFree waits for the frames that use the old buffers)
+static hipError_t grow_pairs(SplatWorkspace* w, size_t K, bool keys) {
+  hipError_t e;
+  if ((e = ensure(w->pairs, K * 8))) return e;
+  if ((e = ensure(w->vals_out, K * 4))) return e;
+  if (keys && (e = ensure(w->keys_out, K * 8))) return e;
+  return hipSuccess;
+}
+// Grow the spill pool to `pairs` (frees the old pool: waits)
+static hipError_t grow_spill(SplatWorkspace* w, uint64_t pairs) {
+  hipError_t e;
+  if ((e = ensure(w->sp_keys, pairs * 8)) || (e = ensure(w->sp_vals, pairs * 4))) return e;
+  w->sp_cap = gs_spill_capacity(w->sp_keys.bytes, w->sp_vals.bytes);
+  return hipSuccess;
+}
+
+// Stage 2: the per-Gaussian and per-tile buffers, sized by the plan alone, and the counter arrays
+static hipError_t gs_ensure_buffers(GsCall& c) {
+  SplatWorkspace* w = c.w;
+  const uint32_t n = c.n, tiles = c.tiles;
+  const BinGrid& bgrid = c.bgrid;
+  hipError_t e;
+  if (c.a->time_stages && !w->ev[0])
     for (hipEvent_t& ev : w->ev)
       if ((e = hipEventCreate(&ev))) return e;
-  w->timed = time_stages;
-  auto mark = [&](int k) -> hipError_t { return time_stages ? hipEventRecord(w->ev[k], s) : hipSuccess; };
-  const uint32_t n = g->count;
-  SplatCam cam;
-  std::memcpy(cam.view, view, sizeof(cam.view));
-  std::memcpy(cam.mvp, mvp, sizeof(cam.mvp));
-  cam.fx = p00 * (float)W * 0.5f;
-  cam.fy = p11 * (float)H * 0.5f;
-  cam.tan_fovx = 1.0f / p00;
-  cam.tan_fovy = 1.0f / (p11 < 0.0f ? -p11 : p11);
-  cam.W = W; cam.H = H;
-  cam.grid_x = (W + GS_BLOCK_X - 1) / GS_BLOCK_X;
-  cam.grid_y = (H + GS_BLOCK_Y - 1) / GS_BLOCK_Y;
-  cam.row_begin = std::min(tile_row_begin, cam.grid_y);
-  cam.row_end = std::min(tile_row_end, cam.grid_y);
-  if (cam.row_end < cam.row_begin) cam.row_end = cam.row_begin;
-  cam.rowcull = (cam.row_begin > 0 || cam.row_end < cam.grid_y) ? 1u : 0u;
-  cam.cull = (g->chunk_bounds && cam.rowcull) ? 1u : 0u;
-  cam.fmax2 = std::max(cam.fx * cam.fx, cam.fy * cam.fy);
-  {  // |W|_2^2 <= the largest Gershgorin row sum of W W^T (W: the view's rotation part; 1 for a lookAt view)
-    double ww[3][3], w2 = 0.0;
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c)
-        ww[r][c] = (double)view[r] * view[c] + (double)view[4 + r] * view[4 + c] + (double)view[8 + r] * view[8 + c];
-    for (int r = 0; r < 3; ++r) w2 = std::max(w2, std::fabs(ww[r][0]) + std::fabs(ww[r][1]) + std::fabs(ww[r][2]));
-    cam.w2 = (float)(w2 * (1.0 + 1e-5));
-  }
-  // stream-ordered frames bin by the alpha box; stats / published frames by the 3-sigma rectangles, unless
-  // PTGS_FLAG_SPLAT_PUBLISH_TIGHT asks for the timed frames' binning (parity tests of their integer outputs)
-  cam.tight = ((!stats && !publish) || (publish && publish_tight)) ? 1u : 0u;
-  const uint32_t tiles = cam.grid_x * cam.grid_y;
-
   if ((e = ensure(w->means2d, (size_t)n * 8))) return e;
   if ((e = ensure(w->depths, (size_t)n * 4))) return e;
   if ((e = ensure(w->conic, (size_t)n * 16))) return e;
@@ -2529,84 +2541,22 @@ hipError_t splat_gaussians(SplatWorkspace* w, const ptgs_gaussians* g, const flo
   if ((e = ensure(w->touched, (size_t)n * 4))) return e;
   if ((e = ensure(w->rect, (size_t)n * 8))) return e;
   if ((e = ensure(w->ranges, (size_t)tiles * 8))) return e;
-  // bands of as many tile rows as fit GS_BAND_TILES (1080p: one band, 4K: four) x chunks of >= GS_CHUNK_MIN
-  // Gaussians, ~256 blocks in all (at most GS_MAX_CHUNKS chunks)
-  if (cam.grid_x > GS_BAND_TILES) return hipErrorInvalidValue;  // W > 131072 px
-  BinGrid bgrid;
-  bgrid.grid_x = cam.grid_x;
-  bgrid.grid_y = cam.grid_y;
-  bgrid.tiles = tiles;
-  if ((tiles + 63u) / 64u > GS_MAX_GROUPS) return hipErrorInvalidValue;
-  bgrid.row0 = cam.row_begin;
-  bgrid.row1 = cam.row_end;
-  const uint32_t brows = cam.row_end - cam.row_begin;  // the frame's tile rows (the bands cover these)
-  bgrid.groups = std::max(1u, (brows * cam.grid_x + 63u) / 64u);
-  bgrid.band_rows = std::max(1u, std::min(std::max(brows, 1u), GS_BAND_TILES / cam.grid_x));
-  bgrid.bands = std::max(1u, (brows + bgrid.band_rows - 1) / bgrid.band_rows);
-  // Chunks: the count / scatter walks are latency-bound loops over a chunk's Gaussians, while every chunk
-  // writes (count), scans (colscan) and reads (scatter) a histogram row of its band's tiles. So 256
-  // workgroups in all as long as the rows cost about as much as the walks; beyond that (at least twice
-  // as many Gaussians per chunk as band tiles: 10M at 4K, a single-band tile-row shard of it) up to
-  // GS_MAX_CHUNKS (10M at 4K: front end 4.3 -> 2.9 ms; 1M at 1080p with 1 024 chunks: 0.289 -> 0.330 ms).
-  const uint32_t band_tiles = bgrid.band_rows * cam.grid_x;
-  const uint32_t want_chunks = std::max(256u / bgrid.bands, (uint32_t)std::min<uint64_t>(GS_MAX_CHUNKS, n / std::max(1u, band_tiles / 2u)));
-  bgrid.chunks = std::max(1u, std::min({(uint32_t)GS_MAX_CHUNKS / bgrid.bands, (n + GS_CHUNK_MIN - 1) / GS_CHUNK_MIN,
-                                        want_chunks}));
-  bgrid.chunk = std::max(1u, (n + bgrid.chunks - 1) / bgrid.chunks);
-  const size_t band_lds = (size_t)bgrid.band_rows * cam.grid_x * 4;
   if ((e = ensure(w->hist, (size_t)bgrid.chunks * tiles * 4))) return e;
   if ((e = ensure(w->nzbuf, (size_t)bgrid.chunks * bgrid.bands * 4))) return e;
   if ((e = ensure(w->tile_slots, (size_t)tiles * GS_TILE_SLOTS * 8))) return e;
   if ((e = ensure(w->tile_info, (size_t)tiles * 8))) return e;
   if ((e = ensure(w->group_total, (size_t)bgrid.groups * 4))) return e;
   if ((e = ensure(w->large, (size_t)tiles * 4))) return e;
-  if (!w->large_ctr.p) {
-    if ((e = ensure(w->large_ctr, 16))) return e;
-    if ((e = hipMemset(w->large_ctr.p, 0, 16))) return e;
-  }
-  if (!w->total.p) {  // [0] = K (scatter), [1] = largest tile (colscan's atomicMax; count re-arms it)
-    if ((e = ensure(w->total, 16))) return e;
-    if ((e = hipMemset(w->total.p, 0, 16))) return e;
-  }
+  if ((e = ensure_zeroed_once(w->large_ctr, GS_LC_WORDS))) return e;
+  if ((e = ensure_zeroed_once(w->total, GS_TOT_WORDS))) return e;
   if (!w->k_host) {
-    if ((e = hipHostMalloc((void**)&w->k_host, 64, hipHostMallocCoherent | hipHostMallocMapped))) return e;
-    std::memset(w->k_host, 0, 64);
+    if ((e = hipHostMalloc((void**)&w->k_host, GS_KH_WORDS * 4u, hipHostMallocCoherent | hipHostMallocMapped))) return e;
+    std::memset(w->k_host, 0, GS_KH_WORDS * 4u);
     if ((e = hipHostGetDevicePointer((void**)&w->k_dev, w->k_host, 0))) return e;
   }
-  if (!w->fz.p) {  // device counters of both front ends, the blend and the spill pool (zero once)
-    if ((e = ensure(w->fz, 256))) return e;
-    if ((e = hipMemsetAsync(w->fz.p, 0, 256, s))) return e;
-  }
-  // An earlier frame of this workspace left a spilled tile incomplete (pool exhausted; k_host[9], a
-  // device store seen once that frame has run) or met an id >= N (k_host[10]): reported by this call,
-  // which renders its own frame after growing the pool (splat_common maps it to PTGS_EINCOMPLETE /
-  // PTGS_EINVAL). A call with stats waits for the earlier frames first (it is synchronous anyway), so
-  // their reports are its own and the flags its superseded runs may raise can be dropped below.
-  if (stats && (e = hipStreamSynchronize(s))) return e;
-  if (__atomic_exchange_n(w->k_host + 9, 0u, __ATOMIC_ACQ_REL)) {
-    ++w->incomplete;
-    *report |= 1u;
-  }
-  if (__atomic_exchange_n(w->k_host + 10, 0u, __ATOMIC_ACQ_REL)) *report |= 2u;
-  // Spill pool: at least max(2^20, N) pairs, the reservation, and 1.25x the demand of the latest
-  // frame whose front end has run (k_host[8]; a hint, no wait). Growth frees the old pool (waits).
-  {
-    const uint32_t demand = w->k_host[8];
-    uint64_t want = std::max<uint64_t>(std::max<uint64_t>(1u << 20, n), w->sp_cap);
-    if (demand > w->sp_cap) want = std::max<uint64_t>(want, (uint64_t)demand + demand / 4u);
-    // a reported frame's own demand reaches k_host[8] only with the NEXT front end: its spilled
-    // tiles hold at most its pair count, which is at most the largest K any frame of the workspace has
-    // published (k_host[12] fused, [13] three launches: device-side running maxima, so a later lighter frame
-    // cannot hide it), so the pool grows to that now and this frame cannot exhaust it the same way
-    if (*report & 1u) {
-      const uint32_t k = std::max({w->k_host[0], w->k_host[12], w->k_host[13]});
-      want = std::max<uint64_t>(want, (uint64_t)k + k / 4u);
-    }
-    want = std::min<uint64_t>(want, 0xFFFFFFF0u);
-    if (want > w->sp_cap || !w->sp_keys.p) {
-      if ((e = ensure(w->sp_keys, want * 8)) || (e = ensure(w->sp_vals, want * 4))) return e;
-      w->sp_cap = (uint32_t)std::min<size_t>(std::min(w->sp_keys.bytes / 8, w->sp_vals.bytes / 4), 0xFFFFFFF0u);
-    }
+  if (!w->fz.p) {  // (zeroed in stream order: the first frame's front end is its first user)
+    if ((e = ensure(w->fz, GS_FZ_WORDS * 4u))) return e;
+    if ((e = hipMemsetAsync(w->fz.p, 0, GS_FZ_WORDS * 4u, c.s))) return e;
   }
 #ifndef GS_K_EVENT_FLAGS
 #define GS_K_EVENT_FLAGS (hipEventDisableTiming | hipEventDisableSystemFence)
@@ -2614,32 +2564,55 @@ hipError_t splat_gaussians(SplatWorkspace* w, const ptgs_gaussians* g, const flo
   // the K event only signals the host (stats requested): k_host is fine-grained (coherent) memory the
   // GPU writes past its caches, so the event needs no system-scope cache release
   if (!w->k_event && (e = hipEventCreateWithFlags(&w->k_event, GS_K_EVENT_FLAGS))) return e;
-  // Pair capacity. The call is stream-ordered: scatter and blend are enqueued against the current
-  // pair buffer and do nothing when the frame's K exceeds it (the device compares). The buffer starts
-  // at 8 pairs per Gaussian and grows from the K that earlier frames' scatters wrote to pinned host
-  // memory (k_host, read here without waiting: a hint); with stats requested the call waits for this
-  // frame's K and re-runs scatter + blend after growing, so that frame is always complete.
-  if (w->pairs.bytes < (size_t)n * 64) {
-    if ((e = ensure(w->pairs, (size_t)n * 64))) return e;
-    if ((e = ensure(w->vals_out, (size_t)n * 32))) return e;
-  }
-  if (publish && (e = ensure(w->keys_out, w->pairs.bytes))) return e;
-  auto cap_now = [&]() -> uint32_t {
-    size_t c = std::min(w->pairs.bytes / 8, w->vals_out.bytes / 4);
-    if (publish) c = std::min(c, w->keys_out.bytes / 8);
-    return (uint32_t)std::min<size_t>(c, 0xFFFFFFFFu);
-  };
-  auto grow = [&](uint32_t K) -> hipError_t {  // (hipFree waits for the frames that use the old buffers)
-    hipError_t e2;
-    if ((e2 = ensure(w->pairs, (size_t)K * 8))) return e2;
-    if ((e2 = ensure(w->vals_out, (size_t)K * 4))) return e2;
-    if (publish && (e2 = ensure(w->keys_out, (size_t)K * 8))) return e2;
-    return hipSuccess;
-  };
-  if (w->k_host[0] > cap_now() && (e = grow(w->k_host[0]))) return e;
+  return hipSuccess;
+}
 
-  const uint32_t slot_keys = n < (1u << 24) ? 1u : 0u;  // the register sort packs the gaussian in 24 bits
-  PreArgs pa;
+// Stage 3. An earlier frame of this workspace left a spilled tile incomplete (pool exhausted;
+// GS_KH_INCOMPLETE, a device store seen once that frame has run) or met an id >= N (GS_KH_BAD_IDS):
+// reported by this call, which renders its own frame after growing the pool (splat_common maps it to
+// PTGS_EINCOMPLETE / PTGS_EBADIDS). A call with stats waits for the earlier frames first (it is synchronous
+// anyway), so their reports are its own and the flags its superseded runs may raise can be dropped later.
+static hipError_t gs_collect_reports(const GsCall& c, uint32_t* report) {
+  SplatWorkspace* w = c.w;
+  hipError_t e;
+  if (c.a->stats && (e = hipStreamSynchronize(c.s))) return e;
+  if (__atomic_exchange_n(w->k_host + GS_KH_INCOMPLETE, 0u, __ATOMIC_ACQ_REL)) {
+    ++w->incomplete;
+    *report |= SPLAT_REPORT_INCOMPLETE;
+  }
+  if (__atomic_exchange_n(w->k_host + GS_KH_BAD_IDS, 0u, __ATOMIC_ACQ_REL)) *report |= SPLAT_REPORT_BAD_IDS;
+  return hipSuccess;
+}
+
+// Stage 4: the spill pool (gs_plan_spill_pool; growth frees the old pool: waits) and the pair buffers.
+// Pair capacity. The call is stream-ordered: scatter and blend are enqueued against the current pair
+// buffer, and a tile whose segment ends beyond it is completed through the spill pool. The buffer starts
+// at 8 pairs per Gaussian and grows from the K that earlier frames wrote to pinned host memory
+// (GS_KH_PAIRS, read here without waiting: a hint); with stats requested the call waits for this frame's
+// K and re-runs scatter + blend after growing, so that frame's published layout is always exact.
+static hipError_t gs_size_pools(const GsCall& c, uint32_t report) {
+  SplatWorkspace* w = c.w;
+  const bool incomplete = (report & SPLAT_REPORT_INCOMPLETE) != 0;
+  hipError_t e;
+  const uint32_t demand = w->k_host[GS_KH_SPILL_DEMAND];
+  const uint32_t largest_k =
+      incomplete ? std::max({w->k_host[GS_KH_PAIRS], w->k_host[GS_KH_MAX_K_FUSED], w->k_host[GS_KH_MAX_K_THREE]}) : 0u;
+  const uint64_t want = gs_plan_spill_pool(c.n, w->sp_cap, demand, incomplete, largest_k);
+  if ((want > w->sp_cap || !w->sp_keys.p) && (e = grow_spill(w, want))) return e;
+  if (w->pairs.bytes < (size_t)c.n * 64 && (e = grow_pairs(w, (size_t)c.n * 8, false))) return e;
+  if (c.a->publish && (e = ensure(w->keys_out, w->pairs.bytes))) return e;
+  if (w->k_host[GS_KH_PAIRS] > pair_capacity(w, c.a->publish) && (e = grow_pairs(w, w->k_host[GS_KH_PAIRS], c.a->publish)))
+    return e;
+  return hipSuccess;
+}
+
+// Stage 5, first: the front ends' per-Gaussian arguments and the buffers only they use
+static hipError_t gs_front_end_args(GsCall& c) {
+  SplatWorkspace* w = c.w;
+  const ptgs_gaussians* g = c.a->g;
+  const uint32_t n = c.n;
+  hipError_t e;
+  PreArgs& pa = c.pa;
   pa.means = g->means;
   pa.scales = g->scales;
   pa.rots = g->rotations;
@@ -2655,345 +2628,378 @@ hipError_t splat_gaussians(SplatWorkspace* w, const ptgs_gaussians* g, const flo
   pa.rec = (float4*)w->rec.p;
   pa.ids = g->ids;
   pa.dbg_depths = (float*)w->dbg_depths.p;
-  pa.bad_ids = w->k_dev + 10;
+  pa.bad_ids = w->k_dev + GS_KH_BAD_IDS;
   // chunks whose bound misses the rows are skipped by the front end before their loads: the fused
   // kernel tests its own chunk's bound; the three-launch count reads flags of a small launch before it
   pa.cskip = nullptr;
-  pa.cbounds = cam.cull ? (const float4*)g->chunk_bounds : nullptr;
-  if (cam.cull) {
-    const uint32_t nch = (n + 255u) / 256u;
-    if ((e = ensure(w->cskip, nch))) return e;
+  pa.cbounds = c.cam.cull ? (const float4*)g->chunk_bounds : nullptr;
+  if (c.cam.cull) {
+    if ((e = ensure(w->cskip, gs_chunks256(n)))) return e;
     pa.cskip = (const uint8_t*)w->cskip.p;
   }
-  auto cull_flags = [&](hipStream_t cs) -> hipError_t {
-    if (!cam.cull) return hipSuccess;
-    const uint32_t nch = (n + 255u) / 256u;
-    hipLaunchKernelGGL(gs_chunk_cull_kernel, dim3((nch + 255u) / 256u), dim3(256), 0, cs, cam,
-                       (const float4*)g->chunk_bounds, nch, (uint8_t*)w->cskip.p);
-    return hipGetLastError();
-  };
-  if (!publish) {  // the per-Gaussian debug outputs only for a published frame (ptgs_splat_get_buffers)
+  if (!c.a->publish) {  // the per-Gaussian debug outputs only for a published frame (ptgs_splat_get_buffers)
     pa.radii = nullptr;
     pa.touched = nullptr;
     pa.means2d = nullptr;
     pa.conic_o = nullptr;
     pa.dbg_depths = nullptr;
   }
-  // Front end: the fused single launch (gs_bin_fused_kernel) once an earlier frame of this workspace
-  // has published its largest tile (the rows' capacity scap follows it with 1/4 headroom, a power of
-  // two in [256, GS_FUSED_MAX_SCAP]); otherwise, or above that capacity, count + colscan + scatter.
-#ifndef GS_FUSED_MAX_SCAP
-#define GS_FUSED_MAX_SCAP 2048u  // larger tiles (1M Gaussians at 1080p): three launches measured faster
-#endif
-#ifndef GS_FUSED_RUNS_PER_TILE
-#define GS_FUSED_RUNS_PER_TILE 32u  // (C2 Morton order: 6; random order: 51; orbit views up to ~20, where
-                                    // fused measured 0.13 vs 0.24 ms for three launches)
-#endif
-  // policy (PTGS_GS_FRONTEND unset): the fused path while frames touch at most
-  // GS_FUSED_RUNS_PER_TILE (workgroup, tile) runs per tile (Gaussians in a spatially coherent order:
-  // each workgroup touches a compact set of tiles; in random order every workgroup touches most tiles
-  // and the reservations cost more than the histograms), else three launches
-  static const int frontend = [] {
-    const char* v = getenv("PTGS_GS_FRONTEND");  // "fused" / "three" (A/B switch)
-    if (v && !strcmp(v, "three")) return 0;
-    if (v && !strcmp(v, "fused")) return 1;
+  // per front-end workgroup chunk rects (gs_spill_tile): fused (bands x 256-Gaussian chunks) or count
+  if ((e = ensure(w->crect, (size_t)std::max(c.nwg_fused, c.bgrid.bands * c.bgrid.chunks) * 8))) return e;
+  c.order = nullptr;
+  if (c.rows) {
+    if ((e = ensure(w->order, (size_t)c.tiles * 4))) return e;
+    c.order = (uint32_t*)w->order.p;
+  }
+  return hipSuccess;
+}
+
+// the environment's A/B switches
+static int gs_env_frontend() {  // PTGS_GS_FRONTEND = "three" (0) / "fused" (1); unset: the policy (2)
+  static const int v = [] {
+    const char* s = getenv("PTGS_GS_FRONTEND");
+    if (s && !strcmp(s, "three")) return 0;
+    if (s && !strcmp(s, "fused")) return 1;
     return 2;
   }();
-  // both front ends publish the frame's touched (workgroup, tile) runs (k_host[4]: the fused kernel's
-  // reservations, the count kernel's nonzero histogram entries); the latest one decides, so the
-  // choice is made from the first finished frame on and follows the data's coherence both ways
-  const bool want_fused = frontend == 1 || (frontend == 2 && w->k_host[4] <= GS_FUSED_RUNS_PER_TILE * tiles);
-  uint32_t scap = 0;
-  if (want_fused && w->have_hint && n) {
-    const uint32_t big = std::max(256u, w->k_host[1] + w->k_host[1] / 4u);
-    uint32_t c = 256;
-    while (c < big && c < GS_FUSED_MAX_SCAP) c <<= 1;
-    if (big <= GS_FUSED_MAX_SCAP && (size_t)tiles * c * 8 <= ((size_t)4 << 30)) scap = c;
+  return v;
+}
+static bool gs_env_helpers_always() {  // PTGS_GS_HELPERS = "always"
+  static const bool v = [] {
+    const char* s = getenv("PTGS_GS_HELPERS");
+    return s && !strcmp(s, "always");
+  }();
+  return v;
+}
+static int gs_env_fe_wg() {  // PTGS_GS_FE_WG = 256 / 512
+  static const int v = [] {
+    const char* s = getenv("PTGS_GS_FE_WG");
+    return s ? atoi(s) : 0;
+  }();
+  return v;
+}
+
+static hipError_t gs_cull_flags(const GsCall& c, hipStream_t cs) {
+  if (!c.cam.cull) return hipSuccess;
+  const uint32_t nch = gs_chunks256(c.n);
+  hipLaunchKernelGGL(gs_chunk_cull_kernel, dim3((nch + 255u) / 256u), dim3(256), 0, cs, c.cam,
+                     (const float4*)c.a->g->chunk_bounds, nch, (uint8_t*)c.w->cskip.p);
+  return hipGetLastError();
+}
+
+// the sort's and the blend's view of a three-launch frame
+static GsFused gs_not_fused(const GsCall& c) {
+  const SplatSeq* seq = c.a->seq;
+  return {0u, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, c.order, nullptr, 0u,
+          seq ? seq->flag : nullptr, seq ? seq->ordinal : 0ull};
+}
+
+static hipError_t gs_blend(const GsCall& c, uint32_t cap, const GsFused& fu, unsigned long long* keys_out,
+                           bool sort_large) {
+  if (c.rows == 0) return hipSuccess;
+  SplatWorkspace* w = c.w;
+  const SplatArgs& a = *c.a;
+  const bool fused_fe = fu.scap != 0;
+  GsSpill sp;
+  sp.fz = (uint32_t*)w->fz.p;
+  sp.k_host = w->k_dev;
+  sp.keys = (unsigned long long*)w->sp_keys.p;
+  sp.vals = (uint32_t*)w->sp_vals.p;
+  sp.cap = w->sp_cap;
+  sp.crect = (const ushort4*)w->crect.p;
+  sp.bands = c.bgrid.bands;
+  sp.chunk = fused_fe ? GS_FUSED_THREADS : c.bgrid.chunk;
+  sp.nwg = fused_fe ? c.nwg_fused : c.bgrid.bands * c.bgrid.chunks;
+  sp.n = c.n;
+  sp.rects = (const ushort4*)w->rect.p;
+  sp.depths = (const float*)w->depths.p;
+  sp.ids = a.g->ids;
+  auto k = a.depth ? gs_sort_blend_kernel<true> : gs_sort_blend_kernel<false>;
+  const dim3 grid(c.cam.grid_x, c.rows);
+  hipLaunchKernelGGL(k, grid, dim3(GS_BLOCK), 0, c.s, c.cam, (const uint2*)w->ranges.p, (unsigned long long*)w->pairs.p,
+                     sort_large ? (uint32_t)GS_MID : 0xFFFFFFFFu, keys_out, (uint32_t*)w->vals_out.p,
+                     (const float4*)w->rec.p, a.bg[0], a.bg[1], a.bg[2], cap, c.slot_keys,
+                     (const unsigned long long*)w->tile_slots.p, a.depth, (const float4*)a.under, (float4*)a.out, fu, sp);
+  const hipError_t le = hipGetLastError();
+  if (!le && a.seq && fu.seq_flag) a.seq->launched = true;
+  return le;
+}
+
+// Tiles above GS_MID pairs: sorted by gs_sort_large_kernel ahead of the blend when the previous frame had
+// any (else the blend sorts the rare one itself). Fused: no tile list, every workgroup checks up to
+// GS_SORT_THREADS tiles by their cursors. Three launches (cap: the pair capacity): tiles beyond the LDS
+// capacity sort in a global scratch ([2][g_cap] u32 + [2][g_cap] u16 at the pair offsets), allocated once a
+// frame has had such tiles.
+static hipError_t gs_sort_large(const GsCall& c, uint32_t cap, const GsFused& fu, unsigned long long* keys_out) {
+  SplatWorkspace* w = c.w;
+  hipError_t e;
+  if (!w->sort_attr) {
+    if ((e = hipFuncSetAttribute((const void*)gs_sort_large_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)gs_radix_lds(GS_RADIX_MAXR))))
+      return e;
+    w->sort_attr = true;
   }
-  const uint32_t rows = cam.row_end - cam.row_begin;
-  // per front-end workgroup chunk rects (gs_spill_tile): fused (bands x 256-Gaussian chunks) or count
-  const uint32_t nwg_fused = bgrid.bands * ((n + GS_FUSED_THREADS - 1) / GS_FUSED_THREADS);
-  if ((e = ensure(w->crect, (size_t)std::max(nwg_fused, bgrid.bands * bgrid.chunks) * 8))) return e;
-  auto spill_args = [&](bool fused_fe) -> GsSpill {
-    GsSpill sp;
-    sp.fz = (uint32_t*)w->fz.p;
-    sp.k_host = w->k_dev;
-    sp.keys = (unsigned long long*)w->sp_keys.p;
-    sp.vals = (uint32_t*)w->sp_vals.p;
-    sp.cap = w->sp_cap;
-    sp.crect = (const ushort4*)w->crect.p;
-    sp.bands = bgrid.bands;
-    sp.chunk = fused_fe ? GS_FUSED_THREADS : bgrid.chunk;
-    sp.nwg = fused_fe ? nwg_fused : bgrid.bands * bgrid.chunks;
-    sp.n = n;
-    sp.rects = (const ushort4*)w->rect.p;
-    sp.depths = (const float*)w->depths.p;
-    sp.ids = g->ids;
-    return sp;
-  };
-  auto blend = [&](uint32_t cap, const GsFused& fu, unsigned long long* keys_out, bool sort_large) -> hipError_t {
-    if (rows == 0) return hipSuccess;
-    auto k = depth ? gs_sort_blend_kernel<true> : gs_sort_blend_kernel<false>;
-    const dim3 grid(cam.grid_x, rows);
-    hipLaunchKernelGGL(k, grid, dim3(GS_BLOCK), 0, s, cam, (const uint2*)w->ranges.p, (unsigned long long*)w->pairs.p,
-                       sort_large ? (uint32_t)GS_MID : 0xFFFFFFFFu, keys_out, (uint32_t*)w->vals_out.p,
-                       (const float4*)w->rec.p, bg[0], bg[1], bg[2], cap, slot_keys,
-                       (const unsigned long long*)w->tile_slots.p, depth, (const float4*)under, (float4*)out, fu,
-                       spill_args(fu.scap != 0));
-    const hipError_t le = hipGetLastError();
-    if (!le && seq && fu.seq_flag) seq->launched = true;
-    return le;
-  };
-  auto sort_attr = [&]() -> hipError_t {
-    if (w->sort_attr) return hipSuccess;
-    hipError_t e2 = hipFuncSetAttribute((const void*)gs_sort_large_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)gs_radix_lds(GS_RADIX_MAXR));
-    if (!e2) w->sort_attr = true;
+  uint32_t g_cap = 0;
+  if (!fu.scap && gs_plan_sort_scratch(w->k_host[GS_KH_MAX_TILE])) {
+    if ((e = ensure(w->sort_scratch, (size_t)cap * 12u))) return e;
+    g_cap = (uint32_t)std::min<size_t>(w->sort_scratch.bytes / 12u, 0xFFFFFFFFu);
+  }
+  uint32_t* g_dep = g_cap ? (uint32_t*)w->sort_scratch.p : nullptr;
+  uint16_t* g_slot = g_cap ? (uint16_t*)(g_dep + 2 * (size_t)g_cap) : nullptr;
+  const uint32_t grid = fu.scap ? gs_plan_sort_grid_fused(w->sort_grid, c.tiles) : w->sort_grid;
+  hipLaunchKernelGGL(gs_sort_large_kernel, dim3(grid), dim3(GS_SORT_THREADS), gs_radix_lds(w->sort_r), c.s,
+                     (const uint2*)w->ranges.p, (unsigned long long*)w->pairs.p,
+                     (const unsigned long long*)w->tile_slots.p, (const uint32_t*)w->large.p,
+                     (const uint32_t*)w->large_ctr.p, keys_out, (uint32_t*)w->vals_out.p,
+                     (const uint32_t*)w->total.p, cap, w->sort_r, g_dep, g_slot, g_cap, fu, c.tiles);
+  return hipGetLastError();
+}
+
+// Stage 5, fused: front end (on the overlap's stream, if any), large-tile sort, blend, and for a
+// published frame the compaction into the three-launch layout
+static hipError_t gs_enqueue_fused(const GsCall& c) {
+  SplatWorkspace* w = c.w;
+  const SplatArgs& a = *c.a;
+  const SplatOverlap* ov = c.ov;
+  const SplatCam& cam = c.cam;
+  const hipStream_t s = c.s;
+  const uint32_t tiles = c.tiles, scap = c.scap;
+  hipError_t e2;
+  if ((e2 = ensure(w->tile_slots, (size_t)tiles * scap * 8))) return e2;
+  if ((e2 = ensure(w->vals_out, (size_t)tiles * scap * 4))) return e2;
+  if (a.publish && (e2 = ensure(w->keys_out, (size_t)tiles * scap * 8))) return e2;
+  // the front end's stream: the caller's, or (overlapped frame) the second stream once ov->wait is done
+  const hipStream_t sf = ov ? ov->fe : s;
+  if (ov && ov->wait && (e2 = hipStreamWaitEvent(sf, ov->wait, 0))) return e2;
+  // (or the workspace's reuse from the blend ordinals, SplatSeq: a wait packet on the front end's queue,
+  // which holds no workgroup slots while it waits and puts nothing on the caller's queue)
+  if (ov && ov->wait_flag &&
+      (e2 = hipStreamWaitValue64(sf, (void*)ov->wait_flag, ov->wait_ordinal, hipStreamWaitValueGte, ~0ull)))
     return e2;
-  };
-  // the blend's tile order (heaviest tiles of the previous frame first), built by the front end's
-  // first launch
-  uint32_t* order = nullptr;
-  if (rows) {
-    if ((e = ensure(w->order, (size_t)tiles * 4))) return e;
-    order = (uint32_t*)w->order.p;
+  if (w->cursor.bytes < (size_t)tiles * 4) {  // zero between frames (the blend re-arms what it reads)
+    if ((e2 = ensure(w->cursor, (size_t)tiles * 4))) return e2;
+    if ((e2 = hipMemsetAsync(w->cursor.p, 0, w->cursor.bytes, sf))) return e2;
   }
-  const GsFused no_fu = {0u, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, order, nullptr, 0u,
-                         seq ? seq->flag : nullptr, seq ? seq->ordinal : 0ull};
-
-  auto enqueue_fused = [&]() -> hipError_t {
-    hipError_t e2;
-    if ((e2 = ensure(w->tile_slots, (size_t)tiles * scap * 8))) return e2;
-    if ((e2 = ensure(w->vals_out, (size_t)tiles * scap * 4))) return e2;
-    if (publish && (e2 = ensure(w->keys_out, (size_t)tiles * scap * 8))) return e2;
-    // the front end's stream: the caller's, or (overlapped frame) the second stream once ov->wait is done
-    const hipStream_t sf = ov ? ov->fe : s;
-    if (ov && ov->wait && (e2 = hipStreamWaitEvent(sf, ov->wait, 0))) return e2;
-    // (or the workspace's reuse from the blend ordinals, SplatSeq: a wait packet on the front end's queue,
-    // which holds no workgroup slots while it waits and puts nothing on the caller's queue)
-    if (ov && ov->wait_flag &&
-        (e2 = hipStreamWaitValue64(sf, (void*)ov->wait_flag, ov->wait_ordinal, hipStreamWaitValueGte, ~0ull)))
-      return e2;
-    if (w->cursor.bytes < (size_t)tiles * 4) {  // zero between frames (the blend re-arms what it reads)
-      if ((e2 = ensure(w->cursor, (size_t)tiles * 4))) return e2;
-      if ((e2 = hipMemsetAsync(w->cursor.p, 0, w->cursor.bytes, sf))) return e2;
-    }
-    // helper workgroups only when the latest fused frame queued slices (k_host[11]: a static view whose
-    // chunks all fit one slice launches none; the owners walk any slice no helper takes, so a frame
-    // that queues more than the helpers take is complete anyway). Idle helpers polled the queue until
-    // every owner had published, and their last poll (~3 us sleep) could end the kernel late.
-    static const int helpers_env = [] {
-      const char* v = getenv("PTGS_GS_HELPERS");  // "always" (A/B switch)
-      return v && !strcmp(v, "always") ? 1 : 0;
-    }();
-    const uint32_t queued = w->k_host[11];
-    const uint32_t helpers = helpers_env ? GS_FUSED_HELPERS
-                             : queued ? std::min<uint32_t>(GS_FUSED_HELPERS, queued + queued / 2u + 8u) : 0u;
-    // owners (bands x chunks) and helpers (bands x helpers) each publish their partials
-    const uint32_t nwg = nwg_fused + bgrid.bands * helpers;
-    if ((e2 = ensure(w->fzp, (size_t)nwg * 8))) return e2;
-    // slice queue: room for twice the slices of the largest pair count seen (+ one per owner); zero
-    // once here, re-armed by the blend after every frame
-    const uint32_t qcap = std::max<uint32_t>(4096u, 2u * (w->k_host[0] / GsFusedShape<256>::slice) + nwg_fused);
-    if (w->fsq.bytes < (size_t)qcap * 8) {
-      if ((e2 = ensure(w->fsq, (size_t)qcap * 8))) return e2;
-      if ((e2 = hipMemsetAsync(w->fsq.p, 0, w->fsq.bytes, sf))) return e2;
-    }
-    const uint32_t fsq_cap = (uint32_t)std::min<size_t>(w->fsq.bytes / 8, 0x7FFFFFFFu);
-    GsFused fu = {scap, (uint32_t*)w->cursor.p, (uint32_t*)w->fz.p, w->k_dev, (uint2*)w->ranges.p,
-                  (uint32_t*)w->fzp.p, nwg, order, (uint2*)w->fsq.p, fsq_cap, seq ? seq->flag : nullptr,
-                  seq ? seq->ordinal : 0ull};
-    PreArgs fpa = pa;  // the fused walk keeps rects / depths in registers (band 0 stores them for gs_spill_tile)
-    if (cam.cull && (n + 255u) / 256u > GS_FUSED_OWN_CULL) {
-      if ((e2 = cull_flags(sf))) return e2;
-      fpa.cbounds = nullptr;
-    }
-    fpa.rects = nullptr;
-    fpa.depths = nullptr;
-    BinGrid fg = bgrid;
-    fg.chunks = (n + GS_FUSED_THREADS - 1) / GS_FUSED_THREADS;
-    fg.chunk = GS_FUSED_THREADS;
-    // the tile order: the front end's extra workgroup from the previous frame's counts, or (overlapped,
-    // own_order) a launch behind the front end from this frame's own counts
-    const bool own_order = order && ov && ov->own_order;
-    uint32_t* fe_order = own_order ? nullptr : order;
-    // the workgroup shape (GsFusedShape: 256 work-items beside another frame's blend, else 512; PTGS_GS_FE_WG
-    // overrides: A/B switch) and its histogram window (entries; 0: the whole band; at least the order's buckets)
-    static const int wg_env = [] {
-      const char* v = getenv("PTGS_GS_FE_WG");
-      return v ? atoi(v) : 0;
-    }();
-    const uint32_t fwg = wg_env == 256 || wg_env == 512 ? (uint32_t)wg_env : ov ? (uint32_t)GS_FUSED_WG_OV : (uint32_t)GS_FUSED_WG;
-    const uint32_t cap = fwg == 256 ? GsFusedShape<256>::lds_cap : GsFusedShape<512>::lds_cap;
-    const size_t fe_lds = std::max<size_t>(cap ? std::min<size_t>(band_lds, (size_t)cap * 4u) : band_lds,
-                                           (size_t)GS_ORDER_BUCKETS * 4u);
-    auto fk = fwg == 256 ? (cam.rowcull ? gs_bin_fused_kernel<true, 256> : gs_bin_fused_kernel<false, 256>)
-                         : (cam.rowcull ? gs_bin_fused_kernel<true, 512> : gs_bin_fused_kernel<false, 512>);
-    hipLaunchKernelGGL(fk, dim3(fg.bands, fg.chunks + helpers + (fe_order ? 1u : 0u)), dim3(fwg), fe_lds, sf,
-                       cam, fpa, fg, scap, (uint32_t*)w->cursor.p, (uint32_t*)w->fz.p, (uint32_t*)w->fzp.p,
-                       (unsigned long long*)w->tile_slots.p, (const uint2*)w->ranges.p, fe_order,
-                       cam.row_begin * cam.grid_x, cam.row_end * cam.grid_x, (ushort4*)w->crect.p, (ushort4*)w->rect.p,
-                       (float*)w->depths.p, w->k_dev, (uint2*)w->fsq.p, fsq_cap, (uint32_t)(fe_lds / 4u));
+  const uint32_t helpers = gs_plan_helpers(gs_env_helpers_always(), w->k_host[GS_KH_QUEUED]);
+  // owners (bands x chunks) and helpers (bands x helpers) each publish their partials
+  const uint32_t nwg = c.nwg_fused + c.bgrid.bands * helpers;
+  if ((e2 = ensure(w->fzp, (size_t)nwg * 8))) return e2;
+  // slice queue: zero once here, re-armed by the blend after every frame
+  const uint32_t qcap = gs_plan_queue_cap(w->k_host[GS_KH_PAIRS], c.nwg_fused);
+  if (w->fsq.bytes < (size_t)qcap * 8) {
+    if ((e2 = ensure(w->fsq, (size_t)qcap * 8))) return e2;
+    if ((e2 = hipMemsetAsync(w->fsq.p, 0, w->fsq.bytes, sf))) return e2;
+  }
+  const uint32_t fsq_cap = (uint32_t)std::min<size_t>(w->fsq.bytes / 8, 0x7FFFFFFFu);
+  GsFused fu = {scap, (uint32_t*)w->cursor.p, (uint32_t*)w->fz.p, w->k_dev, (uint2*)w->ranges.p,
+                (uint32_t*)w->fzp.p, nwg, c.order, (uint2*)w->fsq.p, fsq_cap, a.seq ? a.seq->flag : nullptr,
+                a.seq ? a.seq->ordinal : 0ull};
+  PreArgs fpa = c.pa;  // the fused walk keeps rects / depths in registers (band 0 stores them for gs_spill_tile)
+  if (cam.cull && gs_chunks256(c.n) > GS_FUSED_OWN_CULL) {
+    if ((e2 = gs_cull_flags(c, sf))) return e2;
+    fpa.cbounds = nullptr;
+  }
+  fpa.rects = nullptr;
+  fpa.depths = nullptr;
+  BinGrid fg = c.bgrid;
+  fg.chunks = gs_chunks256(c.n);
+  fg.chunk = GS_FUSED_THREADS;
+  // the tile order: the front end's extra workgroup from the previous frame's counts, or (overlapped,
+  // own_order) a launch behind the front end from this frame's own counts
+  const bool own_order = c.order && ov && ov->own_order;
+  uint32_t* fe_order = own_order ? nullptr : c.order;
+  const GsFusedPlan shape = gs_plan_fused_shape(gs_env_fe_wg(), ov != nullptr, c.band_lds);
+  auto fk = shape.wg == 256 ? (cam.rowcull ? gs_bin_fused_kernel<true, 256> : gs_bin_fused_kernel<false, 256>)
+                            : (cam.rowcull ? gs_bin_fused_kernel<true, 512> : gs_bin_fused_kernel<false, 512>);
+  hipLaunchKernelGGL(fk, dim3(fg.bands, fg.chunks + helpers + (fe_order ? 1u : 0u)), dim3(shape.wg), shape.lds, sf,
+                     cam, fpa, fg, scap, (uint32_t*)w->cursor.p, (uint32_t*)w->fz.p, (uint32_t*)w->fzp.p,
+                     (unsigned long long*)w->tile_slots.p, (const uint2*)w->ranges.p, fe_order,
+                     gs_tile_begin(cam), gs_tile_end(cam), (ushort4*)w->crect.p, (ushort4*)w->rect.p,
+                     (float*)w->depths.p, w->k_dev, (uint2*)w->fsq.p, fsq_cap, (uint32_t)(shape.lds / 4u));
+  if ((e2 = hipGetLastError())) return e2;
+  if (own_order) {
+    hipLaunchKernelGGL(gs_tile_order_kernel, dim3(1), dim3(GS_ORDER_THREADS), 0, sf, (const uint32_t*)w->cursor.p,
+                       c.order, gs_tile_begin(cam), gs_tile_end(cam));
     if ((e2 = hipGetLastError())) return e2;
-    if (own_order) {
-      hipLaunchKernelGGL(gs_tile_order_kernel, dim3(1), dim3(GS_ORDER_THREADS), 0, sf, (const uint32_t*)w->cursor.p,
-                         order, cam.row_begin * cam.grid_x, cam.row_end * cam.grid_x);
-      if ((e2 = hipGetLastError())) return e2;
-    }
-    if (ov && ((e2 = hipEventRecord(ov->done, sf)) || (e2 = hipStreamWaitEvent(s, ov->done, 0)))) return e2;
-    if ((e2 = mark(1)) || (e2 = mark(2)) || (e2 = mark(3))) return e2;
-    unsigned long long* keys_out = publish ? (unsigned long long*)w->keys_out.p : nullptr;
-    const bool sort_large = w->k_host[1] > GS_MID;
-    if (sort_large) {
-      if ((e2 = sort_attr())) return e2;
-      const uint32_t grid = std::max(w->sort_grid, (tiles + GS_SORT_THREADS - 1) / GS_SORT_THREADS);
-      hipLaunchKernelGGL(gs_sort_large_kernel, dim3(grid), dim3(GS_SORT_THREADS), gs_radix_lds(w->sort_r), s,
-                         (const uint2*)w->ranges.p, (unsigned long long*)w->pairs.p,
-                         (const unsigned long long*)w->tile_slots.p, (const uint32_t*)w->large.p,
-                         (const uint32_t*)w->large_ctr.p, keys_out, (uint32_t*)w->vals_out.p,
-                         (const uint32_t*)w->total.p, 0u, w->sort_r, (uint32_t*)nullptr, (uint16_t*)nullptr, 0u, fu, tiles);
-      if ((e2 = hipGetLastError())) return e2;
-    }
-    if ((e2 = mark(4)) || (e2 = mark(5))) return e2;
-    if ((e2 = blend(0u, fu, keys_out, sort_large))) return e2;
-    if (publish) {  // compact the published rows into the three-launch layout (tests only)
-      if ((e2 = ensure(w->pub_offs, (size_t)tiles * 4))) return e2;
-      if ((e2 = ensure(w->keys_pub, (size_t)tiles * scap * 8))) return e2;  // (K <= tiles * scap)
-      if ((e2 = ensure(w->vals_pub, (size_t)tiles * scap * 4))) return e2;
-      const uint32_t tb = cam.row_begin * cam.grid_x, te = cam.row_end * cam.grid_x;
-      hipLaunchKernelGGL(gs_publish_scan_kernel, dim3(1), dim3(GS_PUB_THREADS), 0, s, (const uint2*)w->ranges.p, tiles,
-                         tb, te, scap, (uint32_t*)w->pub_offs.p);
-      hipLaunchKernelGGL(gs_publish_copy_kernel, dim3(tiles), dim3(256), 0, s, (const uint2*)w->ranges.p,
-                         (const uint32_t*)w->pub_offs.p, tb, te, scap, (const unsigned long long*)w->keys_out.p,
-                         (const uint32_t*)w->vals_out.p, (unsigned long long*)w->keys_pub.p, (uint32_t*)w->vals_pub.p,
-                         (uint2*)w->ranges.p);
-      if ((e2 = hipGetLastError())) return e2;
-    }
-    if (stats && (e2 = hipEventRecord(w->k_event, s))) return e2;  // K is on the host after the blend
-    return mark(6);
-  };
-
-  auto enqueue_tail = [&](uint32_t cap) -> hipError_t {
-    // (read here, not before: grow() may have moved the published-keys buffer since the last call)
-    unsigned long long* keys_out = publish ? (unsigned long long*)w->keys_out.p : nullptr;
-    hipLaunchKernelGGL(gs_bin_scatter_kernel, dim3(bgrid.bands, bgrid.chunks), dim3(GS_BIN_THREADS),
-                       2 * band_lds + (size_t)bgrid.groups * 4, s, bgrid, (const ushort4*)w->rect.p,
-                       (const float*)w->depths.p, g->ids, n, (const uint32_t*)w->hist.p, (const uint2*)w->tile_info.p,
-                       (const uint32_t*)w->group_total.p, (uint32_t*)w->total.p, (const uint32_t*)w->large_ctr.p, w->k_dev,
-                       (const uint32_t*)w->nzbuf.p, bgrid.bands * bgrid.chunks, cap,
-                       (uint2*)w->ranges.p, (unsigned long long*)w->pairs.p, (unsigned long long*)w->tile_slots.p);
-    hipError_t e2 = hipGetLastError();
-    if (e2) return e2;
-    if (stats && (e2 = hipEventRecord(w->k_event, s))) return e2;  // K is on the host after the scatter
-    if ((e2 = mark(3))) return e2;
-    // tiles above GS_MID pairs: sorted by gs_sort_large_kernel when the previous frame had any (else
-    // the blend sorts the rare one itself)
-    const bool sort_large = w->k_host[1] > GS_MID;
-    if (sort_large) {
-      if ((e2 = sort_attr())) return e2;
-      // tiles beyond the LDS capacity sort in a global scratch ([2][g_cap] u32 + [2][g_cap] u16 at the
-      // pair offsets), allocated once a frame has had such tiles
-      uint32_t g_cap = 0;
-      if (w->k_host[1] > GS_SORT_THREADS * GS_RADIX_MAXR) {
-        if ((e2 = ensure(w->sort_scratch, (size_t)cap * 12u))) return e2;
-        g_cap = (uint32_t)std::min<size_t>(w->sort_scratch.bytes / 12u, 0xFFFFFFFFu);
-      }
-      uint32_t* g_dep = g_cap ? (uint32_t*)w->sort_scratch.p : nullptr;
-      uint16_t* g_slot = g_cap ? (uint16_t*)(g_dep + 2 * (size_t)g_cap) : nullptr;
-      hipLaunchKernelGGL(gs_sort_large_kernel, dim3(w->sort_grid), dim3(GS_SORT_THREADS), gs_radix_lds(w->sort_r), s,
-                         (const uint2*)w->ranges.p, (unsigned long long*)w->pairs.p,
-                         (const unsigned long long*)w->tile_slots.p, (const uint32_t*)w->large.p,
-                         (const uint32_t*)w->large_ctr.p, keys_out, (uint32_t*)w->vals_out.p,
-                         (const uint32_t*)w->total.p, cap, w->sort_r, g_dep, g_slot, g_cap, no_fu, tiles);
-      if ((e2 = hipGetLastError())) return e2;
-    }
-    if ((e2 = mark(4)) || (e2 = mark(5))) return e2;
-    if ((e2 = blend(cap, no_fu, keys_out, sort_large))) return e2;
-    return mark(6);
-  };
-  auto enqueue_three = [&]() -> hipError_t {
-    hipError_t e2;
-    if ((e2 = ensure(w->tile_slots, (size_t)tiles * GS_TILE_SLOTS * 8))) return e2;
-    if ((e2 = cull_flags(s))) return e2;
-    // (n == 0: one chunk of nothing; the count still zeroes the histograms and the colscan publishes K = 0)
-    hipLaunchKernelGGL(cam.rowcull ? gs_bin_count_kernel<true> : gs_bin_count_kernel<false>,
-                       dim3(bgrid.bands, bgrid.chunks + (order ? 1u : 0u)), dim3(GS_COUNT_THREADS),
-                       std::max(band_lds, (size_t)GS_ORDER_BUCKETS * 4), s, cam, pa, bgrid, (uint32_t*)w->hist.p,
-                       (uint32_t*)w->total.p, (uint32_t*)w->large_ctr.p, w->k_dev, (uint32_t*)w->nzbuf.p,
-                       (const uint2*)w->ranges.p, order, cam.row_begin * cam.grid_x, cam.row_end * cam.grid_x,
-                       (uint32_t*)w->fz.p, (ushort4*)w->crect.p);
+  }
+  if (ov && ((e2 = hipEventRecord(ov->done, sf)) || (e2 = hipStreamWaitEvent(s, ov->done, 0)))) return e2;
+  if ((e2 = gs_mark(c, 1)) || (e2 = gs_mark(c, 2)) || (e2 = gs_mark(c, 3))) return e2;
+  unsigned long long* keys_out = a.publish ? (unsigned long long*)w->keys_out.p : nullptr;
+  const bool sort_large = gs_plan_sort_large(w->k_host[GS_KH_MAX_TILE]);
+  if (sort_large && (e2 = gs_sort_large(c, 0u, fu, keys_out))) return e2;
+  if ((e2 = gs_mark(c, 4)) || (e2 = gs_mark(c, 5))) return e2;
+  if ((e2 = gs_blend(c, 0u, fu, keys_out, sort_large))) return e2;
+  if (a.publish) {  // compact the published rows into the three-launch layout (tests only)
+    if ((e2 = ensure(w->pub_offs, (size_t)tiles * 4))) return e2;
+    if ((e2 = ensure(w->keys_pub, (size_t)tiles * scap * 8))) return e2;  // (K <= tiles * scap)
+    if ((e2 = ensure(w->vals_pub, (size_t)tiles * scap * 4))) return e2;
+    const uint32_t tb = gs_tile_begin(cam), te = gs_tile_end(cam);
+    hipLaunchKernelGGL(gs_publish_scan_kernel, dim3(1), dim3(GS_PUB_THREADS), 0, s, (const uint2*)w->ranges.p, tiles,
+                       tb, te, scap, (uint32_t*)w->pub_offs.p);
+    hipLaunchKernelGGL(gs_publish_copy_kernel, dim3(tiles), dim3(256), 0, s, (const uint2*)w->ranges.p,
+                       (const uint32_t*)w->pub_offs.p, tb, te, scap, (const unsigned long long*)w->keys_out.p,
+                       (const uint32_t*)w->vals_out.p, (unsigned long long*)w->keys_pub.p, (uint32_t*)w->vals_pub.p,
+                       (uint2*)w->ranges.p);
     if ((e2 = hipGetLastError())) return e2;
-    if ((e2 = mark(1))) return e2;
-    hipLaunchKernelGGL(gs_bin_colscan_kernel, dim3(bgrid.groups), dim3(GS_COLSCAN_THREADS), 0, s, bgrid, (uint32_t*)w->hist.p,
-                       (uint2*)w->tile_info.p, (uint32_t*)w->group_total.p, (uint32_t*)w->total.p, (uint32_t)GS_MID,
-                       (uint32_t*)w->large.p, (uint32_t*)w->large_ctr.p);
-    if ((e2 = hipGetLastError())) return e2;
-    if ((e2 = mark(2))) return e2;
-    return enqueue_tail(cap_now());
-  };
+  }
+  if (a.stats && (e2 = hipEventRecord(w->k_event, s))) return e2;  // K is on the host after the blend
+  return gs_mark(c, 6);
+}
 
-  if ((e = mark(0))) return e;
-  const bool fused = scap != 0;
-  if ((e = fused ? enqueue_fused() : enqueue_three())) return e;
-  uint32_t K = w->k_host[0];  // without stats: the latest K any frame published (a hint)
-  bool redone = false;
-  if (stats) {
+// Stage 5, three launches: scatter, large-tile sort and blend against a pair buffer of `cap` pairs (run
+// again by stage 6 after growing it)
+static hipError_t gs_enqueue_tail(const GsCall& c, uint32_t cap) {
+  SplatWorkspace* w = c.w;
+  const BinGrid& bgrid = c.bgrid;
+  // (read here, not before: grow_pairs may have moved the published-keys buffer since the last call)
+  unsigned long long* keys_out = c.a->publish ? (unsigned long long*)w->keys_out.p : nullptr;
+  hipLaunchKernelGGL(gs_bin_scatter_kernel, dim3(bgrid.bands, bgrid.chunks), dim3(GS_BIN_THREADS),
+                     2 * c.band_lds + (size_t)bgrid.groups * 4, c.s, bgrid, (const ushort4*)w->rect.p,
+                     (const float*)w->depths.p, c.a->g->ids, c.n, (const uint32_t*)w->hist.p, (const uint2*)w->tile_info.p,
+                     (const uint32_t*)w->group_total.p, (uint32_t*)w->total.p, (const uint32_t*)w->large_ctr.p, w->k_dev,
+                     (const uint32_t*)w->nzbuf.p, bgrid.bands * bgrid.chunks, cap,
+                     (uint2*)w->ranges.p, (unsigned long long*)w->pairs.p, (unsigned long long*)w->tile_slots.p);
+  hipError_t e2 = hipGetLastError();
+  if (e2) return e2;
+  if (c.a->stats && (e2 = hipEventRecord(w->k_event, c.s))) return e2;  // K is on the host after the scatter
+  if ((e2 = gs_mark(c, 3))) return e2;
+  const GsFused no_fu = gs_not_fused(c);
+  const bool sort_large = gs_plan_sort_large(w->k_host[GS_KH_MAX_TILE]);
+  if (sort_large && (e2 = gs_sort_large(c, cap, no_fu, keys_out))) return e2;
+  if ((e2 = gs_mark(c, 4)) || (e2 = gs_mark(c, 5))) return e2;
+  if ((e2 = gs_blend(c, cap, no_fu, keys_out, sort_large))) return e2;
+  return gs_mark(c, 6);
+}
+static hipError_t gs_enqueue_three(const GsCall& c) {
+  SplatWorkspace* w = c.w;
+  const SplatCam& cam = c.cam;
+  const BinGrid& bgrid = c.bgrid;
+  hipError_t e2;
+  if ((e2 = ensure(w->tile_slots, (size_t)c.tiles * GS_TILE_SLOTS * 8))) return e2;
+  if ((e2 = gs_cull_flags(c, c.s))) return e2;
+  // (n == 0: one chunk of nothing; the count still zeroes the histograms and the colscan publishes K = 0)
+  hipLaunchKernelGGL(cam.rowcull ? gs_bin_count_kernel<true> : gs_bin_count_kernel<false>,
+                     dim3(bgrid.bands, bgrid.chunks + (c.order ? 1u : 0u)), dim3(GS_COUNT_THREADS),
+                     std::max(c.band_lds, (size_t)GS_ORDER_BUCKETS * 4), c.s, cam, c.pa, bgrid, (uint32_t*)w->hist.p,
+                     (uint32_t*)w->total.p, (uint32_t*)w->large_ctr.p, w->k_dev, (uint32_t*)w->nzbuf.p,
+                     (const uint2*)w->ranges.p, c.order, gs_tile_begin(cam), gs_tile_end(cam),
+                     (uint32_t*)w->fz.p, (ushort4*)w->crect.p);
+  if ((e2 = hipGetLastError())) return e2;
+  if ((e2 = gs_mark(c, 1))) return e2;
+  hipLaunchKernelGGL(gs_bin_colscan_kernel, dim3(bgrid.groups), dim3(GS_COLSCAN_THREADS), 0, c.s, bgrid, (uint32_t*)w->hist.p,
+                     (uint2*)w->tile_info.p, (uint32_t*)w->group_total.p, (uint32_t*)w->total.p, (uint32_t)GS_MID,
+                     (uint32_t*)w->large.p, (uint32_t*)w->large_ctr.p);
+  if ((e2 = hipGetLastError())) return e2;
+  if ((e2 = gs_mark(c, 2))) return e2;
+  return gs_enqueue_tail(c, pair_capacity(w, c.a->publish));
+}
+
+// Stage 6 (stats requested): wait for this frame's K. A fused frame with a tile above its row capacity, or
+// a three-launch frame above the pair buffer, was completed through the spill pool; a call with stats
+// re-runs it so that its published keys / values / ranges are the exact layout (three launches, grown
+// buffers). *redone: the fused frame was re-run through three launches.
+static hipError_t gs_wait_and_rerun(const GsCall& c, bool fused, uint32_t* K, bool* redone) {
+  SplatWorkspace* w = c.w;
+  const bool publish = c.a->publish;
+  hipError_t e;
+  if ((e = hipEventSynchronize(w->k_event))) return e;
+  *K = w->k_host[GS_KH_PAIRS];
+  if (fused && w->k_host[GS_KH_OVER_SCAP]) {
+    *redone = true;
+    if ((e = gs_mark(c, 0)) || (e = gs_enqueue_three(c))) return e;
     if ((e = hipEventSynchronize(w->k_event))) return e;
-    K = w->k_host[0];
-    // a fused frame with a tile above its row capacity, or a three-launch frame above the pair
-    // buffer, was completed through the spill pool; a call with stats re-runs it so that its published
-    // keys / values / ranges are the exact layout (three launches, grown buffers)
-    if (fused && w->k_host[5]) {
-      redone = true;
-      if ((e = mark(0)) || (e = enqueue_three())) return e;
-      if ((e = hipEventSynchronize(w->k_event))) return e;
-      K = w->k_host[0];
-    }
-    bool regrown = false;
-    if ((!fused || redone) && K > cap_now()) {
-      if ((e = grow(K))) return e;
-      if ((e = mark(2))) return e;
-      if ((e = enqueue_tail(cap_now()))) return e;
-      regrown = true;
-    }
-    if (redone || regrown) {  // the superseded run's spilled tiles may have exhausted the pool: the
-                              // re-run completed the frame, so its report is dropped
-      if ((e = hipStreamSynchronize(s))) return e;
-      __atomic_store_n(w->k_host + 9, 0u, __ATOMIC_RELEASE);
-    }
-    stats->num_rendered = K;
-    stats->tiles_x = cam.grid_x;
-    stats->tiles_y = cam.grid_y;
-    stats->num_visible = 0;
-    stats->fused = fused && !redone ? 1u : 0u;
+    *K = w->k_host[GS_KH_PAIRS];
   }
-  w->last_fused = fused && !redone;
-  w->last_scap = w->last_fused ? scap : 0u;
+  bool regrown = false;
+  if ((!fused || *redone) && *K > pair_capacity(w, publish)) {
+    if ((e = grow_pairs(w, *K, publish))) return e;
+    if ((e = gs_mark(c, 2))) return e;
+    if ((e = gs_enqueue_tail(c, pair_capacity(w, publish)))) return e;
+    regrown = true;
+  }
+  if (*redone || regrown) {  // the superseded run's spilled tiles may have exhausted the pool: the
+                             // re-run completed the frame, so its report is dropped
+    if ((e = hipStreamSynchronize(c.s))) return e;
+    __atomic_store_n(w->k_host + GS_KH_INCOMPLETE, 0u, __ATOMIC_RELEASE);
+  }
+  return hipSuccess;
+}
+
+// Stage 7: what the next frame of this workspace plans from
+static hipError_t gs_record_hints(const GsCall& c, bool fused, uint32_t K) {
+  SplatWorkspace* w = c.w;
+  const SplatArgs& a = *c.a;
+  hipError_t e;
+  w->last_fused = fused;
+  w->last_scap = fused ? c.scap : 0u;
   // the fused path sizes its rows from the largest tile of a finished frame: valid once the host has
   // seen one complete (a frame still in flight has not written its hint yet)
   if (!w->have_hint) {
     if (!w->hint_event && (e = hipEventCreateWithFlags(&w->hint_event, hipEventDisableTiming))) return e;
     if (w->hint_recorded && hipEventQuery(w->hint_event) == hipSuccess) w->have_hint = true;
-    if (!w->hint_recorded || stats) {
-      if ((e = hipEventRecord(w->hint_event, s))) return e;
+    if (!w->hint_recorded || a.stats) {
+      if ((e = hipEventRecord(w->hint_event, c.s))) return e;
       w->hint_recorded = true;
     }
-    if (stats) w->have_hint = true;  // (waited for above)
+    if (a.stats) w->have_hint = true;  // (waited for above)
   }
-  {  // the next frame's large-tile sort: LDS capacity from the largest tile of a recent frame
-     // (k_host[1]; +1/8 headroom), workgroups from its large-tile count (k_host[2]); hints only
-    const uint32_t big = w->k_host[1] + w->k_host[1] / 8u;
-    w->sort_r = std::min((uint32_t)GS_RADIX_MAXR, ((big + GS_SORT_THREADS - 1) / GS_SORT_THREADS) | 1u);
-    w->sort_grid = std::max(64u, std::min(4096u, w->k_host[2] + w->k_host[2] / 4u));
-  }
-  w->last_n = n;
+  // the next frame's large-tile sort, from a recent frame's largest tile and large-tile count; hints only
+  const GsSortPlan sp = gs_plan_sort(w->k_host[GS_KH_MAX_TILE], w->k_host[GS_KH_LARGE_TILES]);
+  w->sort_r = sp.r;
+  w->sort_grid = sp.grid;
+  w->last_n = c.n;
   w->last_k = K;
-  w->last_tiles = tiles;
-  w->last_published = publish && stats;
-  w->last_w = W;
-  w->last_h = H;
-  w->last_full = !depth && cam.row_begin == 0 && cam.row_end == cam.grid_y;
+  w->last_tiles = c.tiles;
+  w->last_published = a.publish && a.stats;
+  w->last_w = a.W;
+  w->last_h = a.H;
+  w->last_full = !a.depth && c.cam.row_begin == 0 && c.cam.row_end == c.cam.grid_y;
   return hipSuccess;
+}
+
+hipError_t splat_gaussians(SplatWorkspace* w, const SplatArgs& a, uint32_t* report) {
+  hipError_t e;
+  *report = 0;
+  w->last_full = false;  // (a call that fails leaves no frame for the backward pass)
+  w->timed = a.time_stages;
+  GsCall c;
+  c.w = w;
+  c.a = &a;
+  c.s = a.stream;
+  c.ov = (a.stats || a.publish || a.time_stages) ? nullptr : a.ov;  // (these frames are synchronous or instrumented: serial)
+  // 1. plan: the camera, the band / chunk grid (no mailbox word involved)
+  c.n = a.g->count;
+  c.cam = gs_plan_cam(a.view, a.mvp, a.p00, a.p11, a.W, a.H, a.tile_row_begin, a.tile_row_end,
+                      a.g->chunk_bounds != nullptr, a.stats != nullptr, a.publish, a.publish_tight);
+  if (!gs_plan_grid(c.cam, c.n, &c.bgrid)) return hipErrorInvalidValue;
+  c.tiles = c.bgrid.tiles;
+  c.rows = c.cam.row_end - c.cam.row_begin;
+  c.band_lds = (size_t)c.bgrid.band_rows * c.cam.grid_x * 4;
+  c.nwg_fused = c.bgrid.bands * gs_chunks256(c.n);
+  c.slot_keys = c.n < (1u << 24) ? 1u : 0u;  // the register sort packs the gaussian in 24 bits
+  // 2 - 4. buffers, the earlier frames' reports, the pools their hints size
+  if ((e = gs_ensure_buffers(c))) return e;
+  if ((e = gs_collect_reports(c, report))) return e;
+  if ((e = gs_size_pools(c, *report))) return e;
+  // 5. the front end (gs_plan_scap, from the latest frame's touched runs and largest tile) and the frame
+  if ((e = gs_front_end_args(c))) return e;
+  c.scap = gs_plan_scap(gs_env_frontend(), w->k_host[GS_KH_RUNS], w->have_hint, c.n, c.tiles, w->k_host[GS_KH_MAX_TILE]);
+  const bool fused = c.scap != 0;
+  if ((e = gs_mark(c, 0))) return e;
+  if ((e = fused ? gs_enqueue_fused(c) : gs_enqueue_three(c))) return e;
+  // 6. with stats: this frame's K, and the exact layout
+  uint32_t K = w->k_host[GS_KH_PAIRS];  // without stats: the latest K any frame published (a hint)
+  bool redone = false;
+  if (a.stats) {
+    if ((e = gs_wait_and_rerun(c, fused, &K, &redone))) return e;
+    a.stats->num_rendered = K;
+    a.stats->tiles_x = c.cam.grid_x;
+    a.stats->tiles_y = c.cam.grid_y;
+    a.stats->num_visible = 0;
+    a.stats->fused = fused && !redone ? 1u : 0u;
+  }
+  // 7. the next frame's hints
+  return gs_record_hints(c, fused && !redone, K);
 }
 
 // ---- spatial order (ptgs_gaussians_sort_spatial) ---------------------------------------------------
@@ -3093,9 +3099,6 @@ hipError_t splat_sort_spatial(const ptgs_gaussians* g, float* means, float* scal
   return done(hipGetLastError());
 }
 
-// pairs: the pair buffer (three launches: a frame of K <= pairs stores every pair) and the spill pool
-// (fused rows: a frame's spilled tiles hold at most K pairs) — a frame of at most `pairs` pairs is always
-// rendered completely, whichever front end runs and whatever its row capacity (hipGraph replays too)
 // ---- chunk bounds (ptgs_gaussians_chunk_bounds) -----------------------------------------------------
 // chunk c = Gaussians [256 c, 256 c + 256): (min x, min y, min z, max |scale|), (max x, max y, max z, 0)
 __global__ __launch_bounds__(256) void gs_chunk_bounds_kernel(const float* __restrict__ means,
@@ -3132,51 +3135,48 @@ __global__ __launch_bounds__(256) void gs_chunk_bounds_kernel(const float* __res
 
 hipError_t splat_chunk_bounds(const ptgs_gaussians* g, float* bounds, hipStream_t s) {
   if (g->count == 0) return hipSuccess;
-  hipLaunchKernelGGL(gs_chunk_bounds_kernel, dim3((g->count + 255u) / 256u), dim3(256), 0, s, g->means, g->scales,
+  hipLaunchKernelGGL(gs_chunk_bounds_kernel, dim3(gs_chunks256(g->count)), dim3(256), 0, s, g->means, g->scales,
                      g->count, (float4*)bounds);
   return hipGetLastError();
 }
 
+// pairs: the pair buffer (three launches: a frame of K <= pairs stores every pair) and the spill pool
+// (fused rows: a frame's spilled tiles hold at most K pairs) — a frame of at most `pairs` pairs is always
+// rendered completely, whichever front end runs and whatever its row capacity (hipGraph replays too)
 hipError_t splat_reserve(SplatWorkspace* w, uint32_t pairs) {
   hipError_t e;
-  if ((e = ensure(w->pairs, (size_t)pairs * 8))) return e;
-  if ((e = ensure(w->vals_out, (size_t)pairs * 4))) return e;
-  if (w->keys_out.p && (e = ensure(w->keys_out, (size_t)pairs * 8))) return e;
-  if (pairs > w->sp_cap) {
-    if ((e = ensure(w->sp_keys, (size_t)pairs * 8)) || (e = ensure(w->sp_vals, (size_t)pairs * 4))) return e;
-    w->sp_cap = (uint32_t)std::min<size_t>(std::min(w->sp_keys.bytes / 8, w->sp_vals.bytes / 4), 0xFFFFFFF0u);
-  }
+  if ((e = grow_pairs(w, pairs, w->keys_out.p != nullptr))) return e;
+  if (pairs > w->sp_cap && (e = grow_spill(w, pairs))) return e;
   return hipSuccess;
 }
 
 hipError_t splat_status(SplatWorkspace* w, bool clear, SplatStatusOut* out) {
   *out = SplatStatusOut{};
-  if (w->k_host && __atomic_exchange_n(w->k_host + 9, 0u, __ATOMIC_ACQ_REL)) ++w->incomplete;
+  if (w->k_host && __atomic_exchange_n(w->k_host + GS_KH_INCOMPLETE, 0u, __ATOMIC_ACQ_REL)) ++w->incomplete;
   out->incomplete = w->incomplete;
   if (clear) w->incomplete = 0;
-  const size_t c = std::min(w->pairs.bytes / 8, w->vals_out.bytes / 4);
-  out->capacity = (uint32_t)std::min<size_t>(c, 0xFFFFFFFFu);
-  out->last_pairs = w->k_host ? w->k_host[0] : 0u;
+  out->capacity = pair_capacity(w, false);
+  out->last_pairs = splat_pair_hint(w);
   out->spill_capacity = w->sp_cap;
   if (w->fz.p) {  // device counters (the caller has drained the workspace's stream)
-    uint32_t fz[16];
-    const hipError_t e = hipMemcpy(fz, w->fz.p, sizeof(fz), hipMemcpyDeviceToHost);
+    uint32_t ctr[GS_FZ_COUNTERS];
+    const hipError_t e = hipMemcpy(ctr, w->fz.p, sizeof(ctr), hipMemcpyDeviceToHost);
     if (e) return e;
-    out->spilled_tiles = fz[9] - w->spilled_base;
-    out->incomplete_tiles = fz[10] - w->incomplete_base;
-    out->spill_demand = std::max(fz[8], fz[11]);
+    out->spilled_tiles = ctr[GS_FZ_SPILLED] - w->spilled_base;
+    out->incomplete_tiles = ctr[GS_FZ_INCOMPLETE] - w->incomplete_base;
+    out->spill_demand = std::max(ctr[GS_FZ_POOL_CURSOR], ctr[GS_FZ_MAX_DEMAND]);
     if (clear) {
-      w->spilled_base = fz[9];
-      w->incomplete_base = fz[10];
+      w->spilled_base = ctr[GS_FZ_SPILLED];
+      w->incomplete_base = ctr[GS_FZ_INCOMPLETE];
     }
   }
   return hipSuccess;
 }
 
-uint32_t splat_pair_hint(const SplatWorkspace* w) { return w->k_host ? w->k_host[0] : 0u; }
+uint32_t splat_pair_hint(const SplatWorkspace* w) { return w->k_host ? w->k_host[GS_KH_PAIRS] : 0u; }
 
 void splat_front_end_info(const SplatWorkspace* w, uint32_t* touched_runs, uint32_t* fused) {
-  *touched_runs = w->k_host ? w->k_host[4] : 0u;
+  *touched_runs = w->k_host ? w->k_host[GS_KH_RUNS] : 0u;
   *fused = w->last_fused ? 1u : 0u;
 }
 
