@@ -570,6 +570,92 @@ __device__ __forceinline__ Hit trace_closest(const DevScene& sc, const Ray& r, u
   }
 }
 
+// PTGS_PT_ANY_SINGLE_EXIT: the any-hit (shadow) walk in trace_closest's shape. One `occluded` flag per lane, the
+// empty stack pops the DONE sentinel (0x7fffffff: no interior index reaches it, bvh.cpp stack_layout; a leaf
+// link is negative), and the walk returns at one place; no return or continue inside the node or the triangle
+// loop. The entered child is the first hit child in slot order (a select chain over the scalar hit masks
+// Box4::hm), child j is pushed when it and an earlier child are hit (mask expressions on the scalar unit, as
+// enter_box4's), no hit child pops. No sort: near-to-far order measured -9% for shadow rays. Any-hit is an OR
+// over the leaves the ray's boxes reach, so neither the push order nor the visiting order changes the result.
+// Every push is under the exec mask of the lanes whose mask bit is set: a lane that is done, or whose child
+// is missed, stores nothing, and the stack depth is that of the walk it replaces (one entered, the other hit
+// children pushed).
+// PTGS_PT_ANY_PARK (with SINGLE_EXIT): the postponed leaf of trace_closest. A lane that reaches a leaf parks it
+// and walks on until every lane in the loop holds a leaf or is done; one leaf routine, one call site. A lane
+// whose leaf occludes drops what its stack still holds (node = DONE). Off: the lanes of a wave already meet at
+// the leaf (the node loop ends when the last of them reaches one), so parking only lets a lane run ahead into
+// nodes that are wasted when its parked leaf occludes.
+// C3 at 64 spp, interleaved (tools/ab_pt.py; profiles/r09_summary.md): the walk before 6 076 Mrays/s, single
+// exit 6 357, single exit with the postponed leaf 6 275. Shadow node step in the ISA: 224 instructions (120
+// VALU, 96 SALU) -> 164 (108, 48); with the postponed leaf 178 (117, 53).
+#ifndef PTGS_PT_ANY_SINGLE_EXIT
+#define PTGS_PT_ANY_SINGLE_EXIT 1
+#endif
+#ifndef PTGS_PT_ANY_PARK
+#define PTGS_PT_ANY_PARK 0
+#endif
+// PTGS_PT_ANY_TRI_FOLD: the shadow leaf's triangle test without tri_isect's early returns (leaf_any below):
+// triangle step 117 instructions (72 VALU, 41 SALU) -> 106 (67, 35); 6 360 against 6 357 Mrays/s, a tie.
+// PTGS_PT_ANY_TRI_PREFETCH: leaf_closest's one-triangle-ahead fetch in the shadow leaf: 6 325, -0.5%; off.
+#ifndef PTGS_PT_ANY_TRI_FOLD
+#define PTGS_PT_ANY_TRI_FOLD 1
+#endif
+#ifndef PTGS_PT_ANY_TRI_PREFETCH
+#define PTGS_PT_ANY_TRI_PREFETCH 0
+#endif
+// One leaf of the any-hit walk: true when a triangle in [tmin, tmax] is hit and accepted. The loop ends at the
+// first such triangle (its one exit: the loop condition).
+template <bool STATS, bool TEX, bool PK>
+__device__ __forceinline__ bool leaf_any(const DevScene& sc, const Ray& r, int leaf, uint32_t seed,
+                                         TraversalCounters& cnt) {
+  uint32_t start, count;
+  leaf_range<PK>(sc, leaf, start, count);
+  bool occ = false;
+#if PTGS_PT_ANY_TRI_PREFETCH
+  float4 na = sc.tris[3u * start], nb = sc.tris[3u * start + 1u], nc = sc.tris[3u * start + 2u];
+#endif
+  for (uint32_t k = 0; k < count && !occ; ++k) {
+    PT_LANE_TICK(cnt, PT_L_ANY_TRI);
+#if PTGS_PT_ANY_TRI_PREFETCH
+    float4 a = na, bb = nb, c = nc;  // (as leaf_closest: the next triangle in flight while this one is tested)
+    asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(bb.x), "+v"(bb.y), "+v"(bb.z), "+v"(bb.w),
+                      "+v"(c.x), "+v"(c.y), "+v"(c.z), "+v"(c.w));
+    if (k + 1 < count) {
+      const float4* tn = sc.tris + 3u * (start + k + 1u);
+      na = tn[0]; nb = tn[1]; nc = tn[2];
+    }
+#else
+    const float4* tp = sc.tris + 3u * (start + k);
+    float4 a = tp[0], bb = tp[1], c = tp[2];
+#endif
+    if (STATS) cnt.tris++;
+#if PTGS_PT_ANY_TRI_FOLD
+    // tri_isect's expressions with its early returns folded into one predicate: the same operations in the
+    // same order give the same u, v, t wherever tri_isect returns true, and where it returns false early
+    // (det == 0: inv_det is infinite) the first term is false. A wave of shadow rays almost never has every
+    // lane fail the same early test, so the branches bought nothing and cost a dependent load of v0.
+    const v3 e1 = mk3(bb.x, bb.y, bb.z), e2 = mk3(c.x, c.y, c.z);
+    const v3 pvec = cross3(r.d, e2);
+    const float det = dot3(e1, pvec);
+    const float inv_det = 1.0f / det;
+    const v3 tvec = r.o - mk3(a.x, a.y, a.z);
+    const float u = dot3(tvec, pvec) * inv_det;
+    const v3 qvec = cross3(tvec, e1);
+    const float v = dot3(r.d, qvec) * inv_det;
+    const float t = dot3(e2, qvec) * inv_det;
+    bool hit = (det != 0.0f) & !(u < 0.0f) & !(u > 1.0f) & !(v < 0.0f) & !(u + v > 1.0f) & (t >= r.tmin) & (t <= r.tmax);
+#else
+    float t, u, v;
+    bool hit = tri_isect(r, mk3(a.x, a.y, a.z), mk3(bb.x, bb.y, bb.z), mk3(c.x, c.y, c.z), t, u, v);
+    hit = hit && t >= r.tmin && t <= r.tmax;
+#endif
+    if (hit && sc.has_transparent && (sc.tri_flags[start + k] & 1u))
+      hit = anyhit_accept<TEX>(sc, f2u(a.w), f2u(bb.w), u, v, seed, f2u(c.w));
+    occ = hit;
+  }
+  return occ;
+}
+
 template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF, bool N64 = false>  // (as trace_closest)
 __device__ __forceinline__ bool trace_any(const DevScene& sc, const Ray& r, uint32_t seed, int* stack,
                                           TraversalCounters& cnt) {
@@ -577,6 +663,72 @@ __device__ __forceinline__ bool trace_any(const DevScene& sc, const Ray& r, uint
   int sp = 0;
   int node = 0;
   int ovf[OVF > 0 ? OVF : 1];  // entries beyond the LDS part (private: scratch)
+#if PTGS_PT_ANY_SINGLE_EXIT
+  const int DONE = 0x7fffffff;
+  bool occluded = false;
+  auto push = [&](int c) {
+    if (OVF == 0 || sp < PTGS_STACK) stack[sp * SS] = c;
+    else ovf[sp - PTGS_STACK] = c;
+    ++sp;
+  };
+  auto pop = [&]() -> int {
+    if (!sp) return DONE;
+    --sp;
+    return (OVF == 0 || sp < PTGS_STACK) ? stack[sp * SS] : ovf[sp - PTGS_STACK];
+  };
+  int leaf = DONE;  // (PARK: the postponed leaf)
+  for (;;) {
+    while (node >= 0 && node != DONE) {
+      PT_LANE_TICK(cnt, PT_L_ANY_NODE);
+      Box4 b;
+      box4_sel<N64>(rq, sc, node, r.tmax, b);
+      if (STATS) cnt.nodes += 4;
+      const unsigned long long h0 = b.hm[0], h1 = b.hm[1], h2 = b.hm[2], h3 = b.hm[3];
+      const unsigned long long o01 = h0 | h1, o012 = o01 | h2;
+      if (__builtin_amdgcn_inverse_ballot_w64(o012 | h3)) {
+        if (__builtin_amdgcn_inverse_ballot_w64(h0 & h1)) push(b.c[1]);
+        if (__builtin_amdgcn_inverse_ballot_w64(o01 & h2)) push(b.c[2]);
+        if (__builtin_amdgcn_inverse_ballot_w64(o012 & h3)) push(b.c[3]);
+        node = b.c[3];
+        node = __builtin_amdgcn_inverse_ballot_w64(h2) ? b.c[2] : node;
+        node = __builtin_amdgcn_inverse_ballot_w64(h1) ? b.c[1] : node;
+        node = __builtin_amdgcn_inverse_ballot_w64(h0) ? b.c[0] : node;
+      } else {
+        node = pop();
+      }
+      if (PTGS_PT_ANY_PARK) {
+        if (node < 0 && leaf == DONE) {
+          leaf = node;
+          node = pop();
+        }
+        // (every active lane holds a leaf or is done: as trace_closest)
+        if ((__builtin_amdgcn_ballot_w64(leaf != DONE) | __builtin_amdgcn_ballot_w64(node == DONE)) ==
+            __builtin_amdgcn_read_exec())
+          break;
+      }
+    }
+    if (PTGS_PT_ANY_PARK) {
+      if (leaf != DONE) {
+        occluded = leaf_any<STATS, TEX, N64>(sc, r, leaf, seed, cnt);
+        leaf = DONE;
+        if (occluded) node = DONE;
+      }
+      // (a second leaf reached while one was parked: it is the next round's)
+      if (node < 0) {
+        leaf = node;
+        node = pop();
+      }
+      if (node == DONE && leaf == DONE) return occluded;
+    } else {
+      if (node < 0) {
+        occluded = leaf_any<STATS, TEX, N64>(sc, r, node, seed, cnt);
+        node = pop();
+        if (occluded) node = DONE;
+      }
+      if (node == DONE) return occluded;
+    }
+  }
+#else
   auto pop_nz = [&]() -> int {  // sp > 0
     --sp;
     return (OVF == 0 || sp < PTGS_STACK) ? stack[sp * SS] : ovf[sp - PTGS_STACK];
@@ -628,6 +780,7 @@ __device__ __forceinline__ bool trace_any(const DevScene& sc, const Ray& r, uint
     if (sp == 0) return false;
     node = pop_nz();
   }
+#endif
 }
 
 __device__ __forceinline__ v4 matvec(const float* m, v4 v) {

@@ -5,7 +5,11 @@ C3 workload, interleaved rounds in ONE process (cdna_hip_programming.md §5.4 ru
   python tools/ab_pt.py base w4 ...     (variant "base" = libptgs.so)
 
 e.g. the walk without the cull at pop: build.build(defines=("PTGS_PT_STACK_CULL=0",), variant="nocull"), then
-`tools/ab_pt.py nocull base`.
+`tools/ab_pt.py nocull base`. The any-hit (shadow) walk's three forms in one process:
+build.build(defines=("PTGS_PT_ANY_SINGLE_EXIT=0",), variant="anyold") (the walk with two returns and the per-lane
+`have` chain), build.build(defines=("PTGS_PT_ANY_PARK=1",), variant="anypark") (single exit, pushes from the
+scalar hit masks, and the postponed leaf), then `tools/ab_pt.py anyold base anypark` (base: single exit without the
+postponed leaf). The shadow leaf's switches likewise: PTGS_PT_ANY_TRI_FOLD=0, PTGS_PT_ANY_TRI_PREFETCH=1.
 
 AB_SCENE=c5 times C5's mesh instead (the 1M-triangle atrium at 3840x2160, whose tree launches the DEEP
 kernels and whose nodes exceed an XCD's L2); AB_SPP, AB_ROUNDS, AB_CALLS as before. Each variant's image is
