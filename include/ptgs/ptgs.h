@@ -370,6 +370,20 @@ typedef struct ptgs_bvh_buffers {
     uint32_t num_triangles;
 } ptgs_bvh_buffers;
 int ptgs_scene_get_bvh(const ptgs_ctx* ctx, ptgs_bvh_buffers* out);
+/* Which builder produced the resident tree. With PTGS_FLAG_GPU_BVH the upload falls back to the host
+ * build for scenes under 16 triangles and when the GPU build or collapse does not fit its budgets;
+ * `builder` tells the two apart (ptgs_scene_info is the same either way). */
+#define PTGS_BUILDER_HOST_SAH 0u
+#define PTGS_BUILDER_GPU_SAH 1u
+#define PTGS_BUILDER_GPU_LBVH 2u
+typedef struct ptgs_scene_build {
+    uint32_t builder;       /* PTGS_BUILDER_*: the one whose tree is resident */
+    uint32_t leaf, fan;     /* the (leaf size, fan-out) try that was kept (leaf 0 for the LBVH) */
+    uint32_t depth_budget;  /* that try's depth budget */
+    uint32_t stack_need;    /* worst-case traversal stack entries of the resident tree */
+    uint32_t deep_stack;    /* 1 when the deep-stack kernel is launched for it */
+} ptgs_scene_build;
+int ptgs_scene_get_build(const ptgs_ctx* ctx, ptgs_scene_build* out);
 
 /* ---------------- path tracer (raygen_camera.rgen + closesthit/miss/shadow) ---------------- */
 

@@ -178,6 +178,15 @@ class BvhBuffers(C.Structure):
                 ("num_triangles", C.c_uint32)]
 
 
+BUILDER_HOST_SAH, BUILDER_GPU_SAH, BUILDER_GPU_LBVH = 0, 1, 2
+
+
+class SceneBuild(C.Structure):
+    """ptgs_scene_build: which builder produced the resident tree, and the try that was kept."""
+    _fields_ = [("builder", C.c_uint32), ("leaf", C.c_uint32), ("fan", C.c_uint32), ("depth_budget", C.c_uint32),
+                ("stack_need", C.c_uint32), ("deep_stack", C.c_uint32)]
+
+
 assert C.sizeof(Ubo) == 192 and C.sizeof(RayPush) == 80
 
 # (name, restype, argtypes) of every symbol include/ptgs/*.h declares
@@ -195,6 +204,7 @@ SYMBOLS = {
     "ptgs_scene_upload": (_I, [_P, C.POINTER(SceneDesc)]),
     "ptgs_scene_get_info": (_I, [_P, C.POINTER(SceneInfo)]),
     "ptgs_scene_get_bvh": (_I, [_P, C.POINTER(BvhBuffers)]),
+    "ptgs_scene_get_build": (_I, [_P, C.POINTER(SceneBuild)]),
     "ptgs_trace_camera": (_I, [_P, C.POINTER(Ubo), _U, _U, _P, _U, _U, _U, _P]),
     "ptgs_trace_camera_rows": (_I, [_P, C.POINTER(Ubo), _U, _U, _U, _U, _P, _U, _U, _U, _P]),
     "ptgs_trace_torus": (_I, [_P, C.POINTER(Ubo), C.POINTER(RayPush), _P, _U, _P, _P]),

@@ -51,6 +51,7 @@ struct ptgs_ctx {
   DevScene dsc{};
   std::vector<void*> scene_allocs;
   ptgs_scene_info info{};
+  ptgs_scene_build build{};  // which builder's tree is resident (ptgs_scene_get_build)
   unsigned long long* counters = nullptr;  // 8 x u64
   SplatWorkspace* splat = nullptr;
   // ptgs_splat_gaussians_views: views 1.. run on their own workspaces and non-blocking streams,
@@ -386,6 +387,7 @@ int ptgs_scene_upload(ptgs_ctx* c, const ptgs_scene_desc* d) {
 
   free_scene(c);
   c->info = ptgs_scene_info{};
+  c->build = ptgs_scene_build{};
   DevScene s{};
   int rc;
   // BVH: the host binned-SAH build (default), or with PTGS_FLAG_GPU_BVH the GPU LBVH (bvh_gpu.hip),
@@ -404,6 +406,7 @@ int ptgs_scene_upload(ptgs_ctx* c, const ptgs_scene_desc* d) {
     uint32_t built_depth = 0;
     float4* n4 = nullptr;
     uint32_t num4 = 0, need = PTGS_STACK_TOTAL, dep4 = 0;
+    BvhTry kept{0, 0, 0};  // the try whose collapse ran last
     for (int k = 0; k < tries; ++k) {
       const int leaf = lbvh ? 0 : tl[k].leaf, fan = lbvh ? 4 - k : tl[k].fan;
       const uint32_t depth = lbvh ? PTGS_STACK - 1 : tl[k].depth;
@@ -428,6 +431,7 @@ int ptgs_scene_upload(ptgs_ctx* c, const ptgs_scene_desc* d) {
       e = collapse_bvh4_gpu(g.nodes, g.num_nodes, fan, &n4, &num4, &need, &dep4);
       auto t1 = std::chrono::steady_clock::now();
       if (e == hipSuccess) bvh_log("GPU", leaf, fan, depth, dep4, need);
+      kept = BvhTry{leaf, fan, depth};
       ms += (float)std::chrono::duration<double, std::milli>(t1 - t0).count();  // build_ms includes it
       if (e != hipSuccess || need < PTGS_STACK_TOTAL) break;
     }
@@ -451,6 +455,8 @@ int ptgs_scene_upload(ptgs_ctx* c, const ptgs_scene_desc* d) {
       c->info.max_leaf_size = (c->flags & PTGS_FLAG_GPU_LBVH) ? 4u : g.max_leaf;
       c->info.build_ms = ms;
       c->info.device_bytes += (size_t)g.num_nodes * 128 + tris.size() * 52;
+      c->build = ptgs_scene_build{lbvh ? PTGS_BUILDER_GPU_LBVH : PTGS_BUILDER_GPU_SAH, (uint32_t)kept.leaf,
+                                  (uint32_t)kept.fan, kept.depth, need, (uint32_t)s.deep_stack};
       built = true;
     } else if (e == hipErrorNotSupported) {
       (void)hipFree(g.nodes);
@@ -471,6 +477,7 @@ int ptgs_scene_upload(ptgs_ctx* c, const ptgs_scene_desc* d) {
     int built_leaf = -1;
     bool fits = false;
     uint32_t built_depth = 0;
+    BvhTry kept{0, 0, 0};
     for (const BvhTry& tr : bvh_tries()) {
       if (tr.leaf != built_leaf || tr.depth != built_depth) {
         build_bvh(tris, tr.leaf, tr.depth, bvh);
@@ -480,6 +487,7 @@ int ptgs_scene_upload(ptgs_ctx* c, const ptgs_scene_desc* d) {
       }
       fits = collapse_fit(bvh.nodes, n4, num4, dep4, tr.fan, need);
       bvh_log("host", tr.leaf, tr.fan, tr.depth, dep4, need);
+      kept = tr;
       if (fits) break;
     }
     auto t1 = std::chrono::steady_clock::now();
@@ -495,6 +503,8 @@ int ptgs_scene_upload(ptgs_ctx* c, const ptgs_scene_desc* d) {
     c->info.bvh_depth = bvh.depth;
     c->info.max_leaf_size = bvh.max_leaf;
     c->info.build_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    c->build = ptgs_scene_build{PTGS_BUILDER_HOST_SAH, (uint32_t)kept.leaf, (uint32_t)kept.fan, kept.depth, need,
+                                (uint32_t)s.deep_stack};
   }
   // The traversal reads 4-wide nodes through a buffer descriptor with 32-bit byte offsets (node << 7,
   // num_records 0x7fffffff: pt_device.h box4): nodes past 2 GiB would read as zeros (no boxes, child
@@ -573,6 +583,13 @@ int ptgs_scene_get_info(const ptgs_ctx* c, ptgs_scene_info* out) {
   if (!c || !out) return PTGS_EINVAL;
   if (!c->has_scene) return PTGS_ENOSCENE;
   *out = c->info;
+  return PTGS_OK;
+}
+
+int ptgs_scene_get_build(const ptgs_ctx* c, ptgs_scene_build* out) {
+  if (!c || !out) return PTGS_EINVAL;
+  if (!c->has_scene) return PTGS_ENOSCENE;
+  *out = c->build;
   return PTGS_OK;
 }
 

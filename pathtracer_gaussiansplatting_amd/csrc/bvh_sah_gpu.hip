@@ -6,6 +6,11 @@
 // the tree, its node boxes and its leaf ranges equal the host tree's (only the order of the
 // triangles inside a leaf and the BVH2 node numbering differ; the 4-wide collapse renumbers
 // breadth-first, so the BVH4 nodes are identical).
+// One qualifier: the balanced split (past the depth budget, or when the centroids give no SAH
+// candidate) keeps the n / 2 smallest centroids left. Among equal centroids the host leaves the
+// choice to std::nth_element, whose tie order is unspecified; here ties go by position. Where a
+// balanced split meets tied centroids (coincident triangles) the tree is valid, renders the same
+// image, and need not equal the host's (tests/test_bvh_build_gpu.py states what must hold there).
 //
 //   phase A  (tasks of > GS_SAH_T triangles, level by level over all such tasks at once)
 //            bin      one workgroup per 2048-reference chunk of one task: 3 axes x 32 bins of

@@ -16,7 +16,8 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import BvhBuffers, Gaussians, RayPush, SceneInfo, SplatBuffers, SplatStats, SplatStatus, TraceStats, Ubo
+from ._abi import (BvhBuffers, Gaussians, RayPush, SceneBuild, SceneInfo, SplatBuffers, SplatStats, SplatStatus,
+                   TraceStats, Ubo)
 
 
 def _ptr(x) -> int:
@@ -105,6 +106,13 @@ class Renderer:
         info = SceneInfo()
         self._chk(self.lib.ptgs_scene_get_info(self._h, C.byref(info)), "ptgs_scene_get_info")
         return info
+
+    def scene_build(self) -> SceneBuild:
+        """Which builder produced the resident tree (host SAH / GPU SAH / GPU LBVH) and the
+        (leaf, fan, depth budget) try that was kept: a flagged upload may have fallen back."""
+        b = SceneBuild()
+        self._chk(self.lib.ptgs_scene_get_build(self._h, C.byref(b)), "ptgs_scene_get_build")
+        return b
 
     # ---------------------------------------------------------------- path tracer
     def trace_camera(self, ubo: Ubo, width: int, height: int, accum, spp: int = 1, frame_stride: int = 1,

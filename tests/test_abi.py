@@ -63,6 +63,12 @@ def test_struct_layouts():
     assert C.sizeof(_abi.Texture) == 24 and _abi.Texture.srgb.offset == 16
     assert _abi.SceneDesc.textures.offset == _abi.SceneDesc.blue_noise_size.offset + 8
     assert _abi.SceneDesc.num_textures.offset == _abi.SceneDesc.textures.offset + 8
+    # ptgs_scene_build (additive: ptgs_scene_info keeps its 32 bytes)
+    sb = _abi.SceneBuild
+    assert C.sizeof(sb) == 24 and [f[0] for f in sb._fields_] == ["builder", "leaf", "fan", "depth_budget",
+                                                                  "stack_need", "deep_stack"]
+    assert sb.builder.offset == 0 and sb.depth_budget.offset == 12 and sb.deep_stack.offset == 20
+    assert C.sizeof(_abi.SceneInfo) == 32 and _abi.SceneInfo.build_ms.offset == 16
 
 
 def test_compute_path_fails_loudly_without_gpu(native_lib):

@@ -167,14 +167,20 @@ def test_c5_mesh_gpu_sah_build(renderer):
     sc = U.atrium(1_000_000)
     renderer.upload_scene(sc)
     info_h = renderer.scene_info()
+    build_h = renderer.scene_build()
     nodes_h, tris_h = _bvh_arrays(renderer)
     renderer.set_flags(FLAG_GPU_BVH)
     try:
         renderer.upload_scene(sc)
         info_g = renderer.scene_info()
+        build_g = renderer.scene_build()
         nodes_g, tris_g = _bvh_arrays(renderer)
     finally:
         renderer.set_flags(0)
+    # the GPU builder's tree is the resident one (a fallback to the host build would compare equal too)
+    assert build_h.builder == 0 and build_g.builder == 1, (build_h.builder, build_g.builder)
+    assert (build_g.leaf, build_g.fan, build_g.stack_need, build_g.deep_stack) == \
+        (build_h.leaf, build_h.fan, build_h.stack_need, build_h.deep_stack)
     assert info_g.num_triangles == info_h.num_triangles >= 1_000_000
     assert np.array_equal(nodes_g, nodes_h), f"{int(np.count_nonzero(np.any(nodes_g != nodes_h, 1)))} nodes differ"
     assert _leaf_sets_equal(nodes_h, tris_h, tris_g)

@@ -242,14 +242,18 @@ def test_gpu_sah_bvh_is_the_host_tree(renderer, oracle_lib, scene):
     ubo = make_ubo(pose, sc, 0, ambient=(0.3, 0.4, 0.5, 1.0))
     renderer.upload_scene(sc)
     info_h = renderer.scene_info()
+    build_h = renderer.scene_build()
     nodes_h, tris_h = _bvh_arrays(renderer)
     renderer.set_flags(FLAG_GPU_BVH)
     try:
         gpu, st_g = _gpu_render(renderer, sc, ubo, 160, 120, 2)
         info_g = renderer.scene_info()
+        build_g = renderer.scene_build()
         nodes_g, tris_g = _bvh_arrays(renderer)
     finally:
         renderer.set_flags(0)
+    # the GPU builder's tree is the resident one (a fallback to the host build would compare equal too)
+    assert build_h.builder == 0 and build_g.builder == 1, (build_h.builder, build_g.builder)
     assert (info_g.num_bvh_nodes, info_g.bvh_depth) == (info_h.num_bvh_nodes, info_h.bvh_depth)
     assert np.array_equal(nodes_g, nodes_h), f"{int(np.count_nonzero(np.any(nodes_g != nodes_h, 1)))} nodes differ"
     assert _leaf_sets_equal(nodes_h, tris_h, tris_g)
@@ -273,8 +277,10 @@ def test_gpu_lbvh_vs_oracle(renderer, oracle_lib, scene):
     try:
         gpu, st_g = _gpu_render(renderer, sc, ubo, 160, 120, 2)
         info_g = renderer.scene_info()
+        build_g = renderer.scene_build()
     finally:
         renderer.set_flags(0)
+    assert build_g.builder == 2, build_g.builder  # the LBVH's tree, not the host fallback's
     o, so = _oracle_render(oracle_lib, sc, ubo, 160, 120, 2)
     _compare(gpu, o, st_g, so)
     assert np.array_equal(gpu, o)
