@@ -38,7 +38,9 @@ extern "C" {
                              * change (new functions only): ptgs_gaussians_sh_colors, ptgs_gaussians_activate,
                              * ptgs_gaussians_permute_sh, ptgs_splat_gaussians_backward (with the struct
                              * ptgs_gaussian_grads), ptgs_gaussians_sh_colors_backward,
-                             * ptgs_gaussians_activate_backward; ptgs_read_gaussian_ply in ptgs_host.h */
+                             * ptgs_gaussians_activate_backward, ptgs_densify_accumulate,
+                             * ptgs_gaussians_densify_plan, ptgs_gaussians_densify_apply (with their three
+                             * structs); ptgs_read_gaussian_ply in ptgs_host.h */
 
 /* ---------------- error codes ---------------- */
 #define PTGS_OK 0
@@ -705,6 +707,90 @@ int ptgs_splat_gaussians_backward(ptgs_ctx* ctx, const ptgs_gaussians* g, const 
                                   uint32_t width, uint32_t height, const float bg[3],
                                   const float* dL_dout_rgba32f, const ptgs_gaussian_grads* grads,
                                   void* hip_stream);
+
+/* Densification and pruning of a training run (densify_and_prune of Kerbl et al.'s trainer, new Gaussians
+ * inheriting the parent's screen radius), in three steps: a statistic accumulated after every backward, a
+ * plan (decision per Gaussian + scan) and one gather that writes the new arrays. Every float operation is an
+ * IEEE f32 add / sub / mul / div / sqrt in the order written (no FMA, no transcendental: the caller passes the
+ * activated scales and opacities of ptgs_gaussians_activate), so a float32 restatement is reproduced bit for
+ * bit, and no float atomics are used: results are the same from run to run. All arrays are device pointers.
+ *
+ * Common argument handling: PTGS_EINVAL (message in ptgs_last_error, nothing enqueued) for a null ctx or a null
+ * required pointer, or an output that is not a device pointer. n == 0: PTGS_OK before any array pointer is
+ * looked at, nothing is launched (the plan's counts are all zero, and it is a valid plan of 0 -> 0).
+ *
+ * ptgs_densify_accumulate: once per training view, after the backward. g2d (2n) is dL/d(pixel position)
+ * (ptgs_gaussian_grads.means2d), radii (n, int32) the frame's ptgs_splat_buffers.radii, W x H the frame's
+ * size. A Gaussian is visible when radii[i] > 0; for a visible one
+ *   gx = g2d[2i] * (0.5f * W); gy = g2d[2i+1] * (0.5f * H)     (the NDC convention the 0.0002 threshold is stated in)
+ *   accum[i] += sqrt(gx*gx + gy*gy); denom[i] += 1.0f; max_radii[i] = max(max_radii[i], (float)radii[i])
+ * and an invisible one is left untouched. accum / denom / max_radii: n floats each, zero before the first
+ * view. One work-item owns one i. Stream-ordered; allocates nothing.
+ *
+ * ptgs_gaussians_densify_plan: scales (3n) and opacities (n) are the activated values.
+ *   avg  = denom > 0 ? accum / denom : 0;  smax = max(max(s.x, s.y), s.z);  hot = avg >= grad_threshold
+ *   clone = hot && smax <= scale_split;  split = hot && smax > scale_split
+ *   P(o, m, r) = o < min_opacity || (max_screen_radius > 0 && r > max_screen_radius) || (max_scale > 0 && m > max_scale)
+ *   the original survives iff !split && !P(o, smax, r); its clone exists iff clone && !P(o, smax, r);
+ *   its two children exist iff split && !P(o, smax / 1.6f, r)                     (r = max_radii[i])
+ * Output order (the trainer's concatenation order after its masks): surviving originals by source index, clones
+ * by source index, all first children by source index, all second children by source index; total = survivors +
+ * clones + 2 split_sources. The call launches the decision and a two-level exclusive scan, waits for the stream,
+ * returns the counts and leaves in the context's workspace (grown when needed; that may synchronise the
+ * device) a map source[total]: the source index in bits 0..29, the kind in bits 30..31 (0 original, 1 clone,
+ * 2 first child, 3 second child), written stream-ordered for ptgs_gaussians_densify_apply. pruned_originals
+ * counts the originals the prune test removed (a split parent is replaced, not pruned), pruned_children the
+ * children it removed (two per source). n above 2^30 (the index would not fit beside the kind): PTGS_EINVAL.
+ *
+ * ptgs_gaussians_densify_apply consumes the plan the context's latest plan call left: PTGS_EINVAL when there is
+ * none, or when n / n_out differ from its n / total. An original or a clone copies every array's row of its
+ * source. Child k (0, 1) of source i copies its rows too, except
+ *   log_scales' = log_scales - 0.4700036f                                 (ln 1.6: the trainer's / (0.8 * 2))
+ *   mean' = mean + R v, v = scales * noise[k][i]   (noise: float [2][n][3], standard-normal draws of the caller)
+ *   R = the rotation of (w, x, y, z) / len, len = sqrt(((w*w + x*x) + y*y) + z*z); len == 0: the identity
+ *   R = [[1 - 2 (y*y + z*z), 2 (x*y - w*z), 2 (x*z + w*y)], [2 (x*y + w*z), 1 - 2 (x*x + z*z), 2 (y*z - w*x)],
+ *        [2 (x*z - w*y), 2 (y*z + w*x), 1 - 2 (x*x + y*y)]] evaluated as written (the forward projection's order)
+ *   (R v)_r = (R_r0*v0 + R_r1*v1) + R_r2*v2
+ * means / log_scales / rotations (un-normalised) / scales (activated) are the source arrays (3n, 3n, 4n, 3n),
+ * means_out / log_scales_out have 3 n_out floats. rows[0 .. n_rows) (n_rows <= 16, read by the host during the
+ * call) are the other per-Gaussian arrays: rotations, logits, SH coefficients, Adam moments, ...: dst row j
+ * (width floats) = src row of j's source, or zeros when zero_new is set and j is a clone or a child. Any width
+ * >= 1 and any 4-byte-aligned base are accepted (16-byte accesses are used only where base and width allow).
+ * PTGS_EINVAL: n_rows > 16, a width of 0, a null src / dst, or an output (means_out, log_scales_out, a dst,
+ * source_out) that overlaps an input or another output. source_out: NULL, or n_out u32 that receive the map.
+ * n_out == 0 (everything pruned): PTGS_OK, nothing is launched. Stream-ordered; allocates nothing. */
+typedef struct ptgs_densify_params {
+    float grad_threshold;     /* on the averaged statistic (the trainer's 0.0002) */
+    float scale_split;        /* percent_dense x scene extent: clone at or below it, split above */
+    float min_opacity;        /* prune below it (0.005) */
+    float max_scale;          /* prune above it (0.1 x scene extent); 0: test disabled */
+    float max_screen_radius;  /* prune above it, in pixels; 0: test disabled */
+} ptgs_densify_params;
+typedef struct ptgs_densify_counts {
+    uint32_t survivors;
+    uint32_t clones;
+    uint32_t split_sources;
+    uint32_t pruned_originals;
+    uint32_t pruned_children;
+    uint32_t total;
+} ptgs_densify_counts;
+typedef struct ptgs_densify_rows {
+    const float* src;   /* n rows */
+    float* dst;         /* n_out rows */
+    uint32_t width;     /* floats per Gaussian */
+    uint32_t zero_new;  /* != 0: clones and children get zeros (optimizer moments) */
+} ptgs_densify_rows;
+#define PTGS_DENSIFY_MAX_ROWS 16
+int ptgs_densify_accumulate(ptgs_ctx* ctx, const float* g2d, const int32_t* radii, uint32_t n, uint32_t width,
+                            uint32_t height, float* accum, float* denom, float* max_radii, void* hip_stream);
+int ptgs_gaussians_densify_plan(ptgs_ctx* ctx, const float* scales, const float* opacities, const float* accum,
+                                const float* denom, const float* max_radii, uint32_t n,
+                                const ptgs_densify_params* params, ptgs_densify_counts* out, void* hip_stream);
+int ptgs_gaussians_densify_apply(ptgs_ctx* ctx, uint32_t n, uint32_t n_out, const float* means,
+                                 const float* log_scales, const float* rotations, const float* scales,
+                                 const float* noise, float* means_out, float* log_scales_out,
+                                 const ptgs_densify_rows* rows, uint32_t n_rows, uint32_t* source_out,
+                                 void* hip_stream);
 
 /* Report of the stream-ordered splat (no stats): waits for hip_stream and the context's view streams,
  * then returns (and clears) the counts since the last query. frames / views[v]: frames left

@@ -7,6 +7,7 @@ from ._abi import (ACCUM_RUNNING_MEAN, ACCUM_SUM, FLAG_COUNT_TRAVERSAL, FLAG_GPU
                    PUNCTUAL_LIGHT_DTYPE, RAY_SAMPLE_DTYPE, VERTEX_DTYPE, PtgsError, RayPush, Ubo, load_library)
 from . import autograd
 from .capture import load_gaussian_ply
+from .densify import DensifyStats, densify_and_prune
 from .renderer import Renderer, torus_push
 from .scene import Camera, CameraPose, Scene, SceneBuilder, cornell_box_scene, make_ubo, mat4_inverse
 
@@ -14,5 +15,5 @@ __all__ = [
     "ACCUM_RUNNING_MEAN", "ACCUM_SUM", "FLAG_COUNT_TRAVERSAL", "FLAG_GPU_BVH", "FLAG_GPU_LBVH", "FLAG_PT_WAVEFRONT", "FLAG_SPLAT_PUBLISH", "FLAG_TIME_STAGES", "HITDATA_DTYPE", "MATERIAL_DTYPE",
     "PUNCTUAL_LIGHT_DTYPE", "RAY_SAMPLE_DTYPE", "VERTEX_DTYPE", "PtgsError", "RayPush", "Ubo", "load_library",
     "Renderer", "torus_push", "Camera", "CameraPose", "Scene", "SceneBuilder", "cornell_box_scene", "make_ubo",
-    "mat4_inverse", "load_gaussian_ply", "autograd",
+    "mat4_inverse", "load_gaussian_ply", "autograd", "DensifyStats", "densify_and_prune",
 ]

@@ -152,6 +152,26 @@ class GaussianGrads(C.Structure):
                 ("opacities", C.c_void_p), ("colors", C.c_void_p), ("means2d", C.c_void_p), ("conics", C.c_void_p)]
 
 
+class DensifyParams(C.Structure):
+    """ptgs_densify_params: the thresholds of ptgs_gaussians_densify_plan (0 disables max_scale / max_screen_radius)."""
+    _fields_ = [("grad_threshold", C.c_float), ("scale_split", C.c_float), ("min_opacity", C.c_float),
+                ("max_scale", C.c_float), ("max_screen_radius", C.c_float)]
+
+
+class DensifyCounts(C.Structure):
+    """ptgs_densify_counts: total = survivors + clones + 2 split_sources."""
+    _fields_ = [("survivors", C.c_uint32), ("clones", C.c_uint32), ("split_sources", C.c_uint32),
+                ("pruned_originals", C.c_uint32), ("pruned_children", C.c_uint32), ("total", C.c_uint32)]
+
+
+class DensifyRows(C.Structure):
+    """ptgs_densify_rows: one per-Gaussian array that ptgs_gaussians_densify_apply gathers."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_uint32), ("zero_new", C.c_uint32)]
+
+
+DENSIFY_MAX_ROWS = 16
+
+
 class SplatStats(C.Structure):
     _fields_ = [("num_rendered", C.c_uint32), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32),
                 ("num_visible", C.c_uint32), ("fused", C.c_uint32)]
@@ -232,6 +252,11 @@ SYMBOLS = {
     "ptgs_gaussians_permute_sh": (_I, [_P, _P, _U, _P, _U, _P, _P]),
     "ptgs_splat_gaussians_backward": (_I, [_P, C.POINTER(Gaussians), C.POINTER(Ubo), _U, _U, _FP, _P,
                                            C.POINTER(GaussianGrads), _P]),
+    "ptgs_densify_accumulate": (_I, [_P, _P, _P, _U, _U, _U, _P, _P, _P, _P]),
+    "ptgs_gaussians_densify_plan": (_I, [_P, _P, _P, _P, _P, _P, _U, C.POINTER(DensifyParams),
+                                         C.POINTER(DensifyCounts), _P]),
+    "ptgs_gaussians_densify_apply": (_I, [_P, _U, _U, _P, _P, _P, _P, _P, _P, _P, C.POINTER(DensifyRows), _U, _P,
+                                          _P]),
     "ptgs_trace_depth_rows": (_I, [_P, C.POINTER(Ubo), _U, _U, _U, _U, _P, _P]),
     "ptgs_knn3_mean_dist2": (_I, [_P, _P, _U, _P, _P]),
     "ptgs_gaussians_from_points": (_I, [_P, _P, _P, _U, _P, _P, _P, _P, _P, _P]),

@@ -33,6 +33,7 @@
 #include "comm.h"
 #include "splat.h"
 #include "splat_backward.h"
+#include "splat_densify.h"
 #include "splat_sh.h"
 #include "textures.h"
 
@@ -54,6 +55,7 @@ struct ptgs_ctx {
   ptgs_scene_build build{};  // which builder's tree is resident (ptgs_scene_get_build)
   unsigned long long* counters = nullptr;  // 8 x u64
   SplatWorkspace* splat = nullptr;
+  DensifyWorkspace* densify = nullptr;  // the densification plan (ptgs_gaussians_densify_plan / _apply)
   // ptgs_splat_gaussians_views: views 1.. run on their own workspaces and non-blocking streams,
   // forked from / joined back into the caller's stream with events (view 0 uses `splat` on it)
   SplatWorkspace* view_ws[PTGS_MAX_VIEWS] = {};
@@ -208,6 +210,7 @@ int ptgs_create(int hip_device, ptgs_ctx** out) {
   if (hipMalloc(&c->counters, 8 * sizeof(unsigned long long)) != hipSuccess) { delete c; return PTGS_EHIP; }
   if (hipMemset(c->counters, 0, 8 * sizeof(unsigned long long)) != hipSuccess) { delete c; return PTGS_EHIP; }
   c->splat = splat_workspace_create();
+  c->densify = densify_workspace_create();
   *out = c;
   return PTGS_OK;
 }
@@ -219,6 +222,7 @@ void ptgs_destroy(ptgs_ctx* c) {
   if (c->counters) (void)hipFree(c->counters);
   ptgs::wf_workspace_free(c->wf);
   ptgs::free_pt_sched(c->pt_sched);
+  densify_workspace_destroy(c->densify);
   // (c->splat is one of the ring's workspaces once PTGS_FLAG_SPLAT_OVERLAP has been used: ring slot 0 is
   // the context's first one, freed here; the others below)
   splat_workspace_destroy(c->ov_ring[0] ? c->ov_ring[0] : c->splat);
@@ -1164,6 +1168,97 @@ int ptgs_splat_gaussians_backward(ptgs_ctx* c, const ptgs_gaussians* g, const pt
   const hipError_t e = splat_gaussians_backward(f, acc, g, ubo->view, mvp, ubo->proj[0], ubo->proj[5], bg, dL_dout, grads,
                                                 (hipStream_t)stream);
   if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_splat_gaussians_backward: %s", hipGetErrorString(e));
+  return PTGS_OK;
+}
+
+int ptgs_densify_accumulate(ptgs_ctx* c, const float* g2d, const int32_t* radii, uint32_t n, uint32_t w, uint32_t h,
+                            float* accum, float* denom, float* max_radii, void* stream) {
+  if (!c) return PTGS_EINVAL;
+  if (n == 0) return PTGS_OK;  // (empty arrays may be null)
+  if (!g2d || !radii || !accum || !denom || !max_radii) return fail(c, PTGS_EINVAL, "null argument");
+  if (!is_device_ptr(accum) || !is_device_ptr(denom) || !is_device_ptr(max_radii))
+    return fail(c, PTGS_EINVAL, "accum / denom / max_radii must be device pointers");
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipError_t e = densify_accumulate(g2d, radii, n, w, h, accum, denom, max_radii, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_densify_accumulate: %s", hipGetErrorString(e));
+  return PTGS_OK;
+}
+
+int ptgs_gaussians_densify_plan(ptgs_ctx* c, const float* scales, const float* opacities, const float* accum,
+                                const float* denom, const float* max_radii, uint32_t n,
+                                const ptgs_densify_params* params, ptgs_densify_counts* out, void* stream) {
+  if (!c) return PTGS_EINVAL;
+  if (!params || !out) return fail(c, PTGS_EINVAL, "null argument");
+  *out = ptgs_densify_counts{};
+  if (n == 0) {  // (empty arrays may be null)
+    densify_plan_empty(c->densify);
+    return PTGS_OK;
+  }
+  if (!scales || !opacities || !accum || !denom || !max_radii) return fail(c, PTGS_EINVAL, "null argument");
+  if (n > (1u << 30))
+    return fail(c, PTGS_EINVAL, "%u gaussians: the source map holds indices below 2^30 beside the kind", n);
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipError_t e = densify_plan(c->densify, scales, opacities, accum, denom, max_radii, n, *params, out,
+                                    (hipStream_t)stream);
+  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_densify_plan: %s", hipGetErrorString(e));
+  return PTGS_OK;
+}
+
+int ptgs_gaussians_densify_apply(ptgs_ctx* c, uint32_t n, uint32_t n_out, const float* means, const float* log_scales,
+                                 const float* rotations, const float* scales, const float* noise, float* means_out,
+                                 float* log_scales_out, const ptgs_densify_rows* rows, uint32_t n_rows,
+                                 uint32_t* source_out, void* stream) {
+  if (!c) return PTGS_EINVAL;
+  if (n_rows > PTGS_DENSIFY_MAX_ROWS)
+    return fail(c, PTGS_EINVAL, "n_rows %u above %d", n_rows, PTGS_DENSIFY_MAX_ROWS);
+  if (n_rows && !rows) return fail(c, PTGS_EINVAL, "null argument");
+  uint32_t pn = 0, pn_out = 0;
+  if (!densify_last_plan(c->densify, &pn, &pn_out))
+    return fail(c, PTGS_EINVAL, "no plan: ptgs_gaussians_densify_plan must come first");
+  if (pn != n || pn_out != n_out)
+    return fail(c, PTGS_EINVAL, "the latest plan takes %u gaussians to %u, the apply call %u to %u", pn, pn_out, n,
+                n_out);
+  for (uint32_t k = 0; k < n_rows; ++k)
+    if (rows[k].width == 0) return fail(c, PTGS_EINVAL, "rows[%u] has width 0", k);
+  if (n_out == 0) return PTGS_OK;  // everything pruned (or n == 0): nothing to write
+  if (!means || !log_scales || !rotations || !scales || !noise || !means_out || !log_scales_out)
+    return fail(c, PTGS_EINVAL, "null argument");
+  // every input and output as a byte range: an output may overlap nothing else
+  struct Span {
+    const char* p;
+    size_t bytes;
+    bool out;
+  };
+  Span sp[7 + 2 * PTGS_DENSIFY_MAX_ROWS + 1];
+  uint32_t ns = 0;
+  auto span = [&](const void* p, size_t count, size_t width, bool out) {
+    sp[ns++] = Span{(const char*)p, count * width * sizeof(float), out};
+  };
+  span(means, n, 3, false);
+  span(log_scales, n, 3, false);
+  span(rotations, n, 4, false);
+  span(scales, n, 3, false);
+  span(noise, (size_t)n * 2, 3, false);
+  span(means_out, n_out, 3, true);
+  span(log_scales_out, n_out, 3, true);
+  for (uint32_t k = 0; k < n_rows; ++k) {
+    if (!rows[k].src || !rows[k].dst) return fail(c, PTGS_EINVAL, "rows[%u] has a null src / dst", k);
+    span(rows[k].src, n, rows[k].width, false);
+    span(rows[k].dst, n_out, rows[k].width, true);
+  }
+  if (source_out) span(source_out, n_out, 1, true);
+  for (uint32_t i = 0; i < ns; ++i) {
+    if (!sp[i].out) continue;
+    for (uint32_t j = 0; j < ns; ++j)
+      if (j != i && (j > i || !sp[j].out) && sp[i].p < sp[j].p + sp[j].bytes && sp[j].p < sp[i].p + sp[i].bytes)
+        return fail(c, PTGS_EINVAL, "an output aliases an input or another output (every dst differs from every src)");
+    if (!is_device_ptr(sp[i].p)) return fail(c, PTGS_EINVAL, "an output is not a device pointer");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipError_t e = densify_apply(c->densify, means, log_scales, rotations, scales, noise, means_out, log_scales_out,
+                                     rows, n_rows, source_out, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(c, PTGS_ERANGE, "ptgs_gaussians_densify_apply: more elements than one launch holds");
+  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_densify_apply: %s", hipGetErrorString(e));
   return PTGS_OK;
 }
 

@@ -420,6 +420,82 @@ class Renderer:
         self._chk(rc, "ptgs_gaussians_activate_backward")
         return ds, do
 
+    # ---------------------------------------------------------------- densification and pruning
+    def densify_accumulate(self, means2d_grad, width: int, height: int, accum, denom, max_radii, radii=None,
+                           stream=None):
+        """ptgs_densify_accumulate: one training view's densification statistic. means2d_grad [N, 2] is
+        dL/d(pixel position) of the backward just run (splat_sh(..., means2d_grad=)); radii (int32 [N]) default
+        to the published frame's own (the latest splat of this renderer, which must have N Gaussians). Visible
+        Gaussians (radius > 0) add the NDC-scaled gradient norm to accum, 1 to denom and raise max_radii
+        (float32 [N] each, updated in place). Stream-ordered; reproducible (no atomics)."""
+        import torch
+        n = int(means2d_grad.shape[0])
+        self._f32(("means2d_grad", means2d_grad, n * 2), ("accum", accum, n), ("denom", denom, n),
+                  ("max_radii", max_radii, n))
+        if radii is None:
+            b = self.splat_buffers()
+            if b.num_gaussians != n or (n and not b.radii):
+                raise _abi.PtgsError(f"the published frame has {b.num_gaussians} gaussians, the statistic {n}: "
+                                     "densify_accumulate follows a published splat of the same Gaussians")
+            rp = b.radii or 0
+        else:
+            if radii.dtype != torch.int32 or radii.numel() != n:
+                raise _abi.PtgsError(f"radii must be int32 with {n} elements (got {radii.dtype}, {radii.numel()})")
+            rp = _ptr(radii)
+        rc = self.lib.ptgs_densify_accumulate(self._h, _ptr(means2d_grad), rp, n, int(width), int(height), _ptr(accum),
+                                              _ptr(denom), _ptr(max_radii), _stream(stream))
+        self._chk(rc, "ptgs_densify_accumulate")
+
+    def densify_plan(self, scales, opacities, accum, denom, max_radii, *, grad_threshold: float, scale_split: float,
+                     min_opacity: float, max_scale: float = 0.0, max_screen_radius: float = 0.0,
+                     stream=None) -> _abi.DensifyCounts:
+        """ptgs_gaussians_densify_plan: decide clone / split / prune for every Gaussian from its ACTIVATED scales
+        [N, 3] and opacities [N] and the accumulated statistic, and leave the source map of the new set in the
+        context for densify_apply. Waits for the stream; returns the counts (.total = the new N)."""
+        n = int(opacities.shape[0])
+        self._f32(("scales", scales, n * 3), ("opacities", opacities, n), ("accum", accum, n), ("denom", denom, n),
+                  ("max_radii", max_radii, n))
+        p = _abi.DensifyParams(float(grad_threshold), float(scale_split), float(min_opacity), float(max_scale),
+                               float(max_screen_radius))
+        out = _abi.DensifyCounts()
+        rc = self.lib.ptgs_gaussians_densify_plan(self._h, _ptr(scales), _ptr(opacities), _ptr(accum), _ptr(denom),
+                                                  _ptr(max_radii), n, C.byref(p), C.byref(out), _stream(stream))
+        self._chk(rc, "ptgs_gaussians_densify_plan")
+        return out
+
+    def densify_apply(self, n_out: int, means, log_scales, rotations, scales, noise, rows=(), want_source=False,
+                      stream=None):
+        """ptgs_gaussians_densify_apply: the new arrays of the latest densify_plan (n_out = its .total).
+        rotations [N, 4] and the ACTIVATED scales [N, 3] place the split children with noise (float32 [2, N, 3]
+        standard-normal draws). rows: (tensor [N, ...], zero_new) pairs, every other per-Gaussian array
+        (rotations, logits, SH, optimizer moments; zero_new: clones and children get zeros), at most 16.
+        Returns (means_out, log_scales_out, [row outputs, shaped [n_out, ...]], source or None): source is the
+        uint32 map (source index | kind << 30) as an int32 tensor when want_source. Stream-ordered."""
+        import torch
+        n, n_out = int(means.shape[0]), int(n_out)
+        self._f32(("means", means, n * 3), ("log_scales", log_scales, n * 3), ("rotations", rotations, n * 4),
+                  ("scales", scales, n * 3), ("noise", noise, n * 6))
+        dev = means.device
+        new = lambda t: torch.empty((n_out,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)  # noqa: E731
+        means_out, ls_out = new(means), new(log_scales)
+        if len(rows) > _abi.DENSIFY_MAX_ROWS:
+            raise _abi.PtgsError(f"{len(rows)} rows: at most {_abi.DENSIFY_MAX_ROWS}")
+        arr = (_abi.DensifyRows * max(1, len(rows)))()
+        outs = []
+        for k, (t, zero_new) in enumerate(rows):
+            if t.shape[0] != n or t.numel() == 0 and n:
+                raise _abi.PtgsError(f"rows[{k}] must have {n} non-empty rows (got {tuple(t.shape)})")
+            self._f32((f"rows[{k}]", t, t.numel()))
+            outs.append(new(t))
+            arr[k].src, arr[k].dst = _ptr(t), _ptr(outs[-1])
+            arr[k].width, arr[k].zero_new = (t.numel() // n if n else 1), int(bool(zero_new))
+        source = torch.empty(n_out, dtype=torch.int32, device=dev) if want_source else None
+        rc = self.lib.ptgs_gaussians_densify_apply(self._h, n, n_out, _ptr(means), _ptr(log_scales), _ptr(rotations),
+                                                   _ptr(scales), _ptr(noise), _ptr(means_out), _ptr(ls_out), arr,
+                                                   len(rows), _ptr(source), _stream(stream))
+        self._chk(rc, "ptgs_gaussians_densify_apply")
+        return means_out, ls_out, outs, source
+
     def permute_sh(self, sh, ids, stream=None):
         """ptgs_gaussians_permute_sh: sh[ids] as a new tensor: the SH rows of the copy that
         sort_gaussians_spatial returned with these ids."""
