@@ -6,12 +6,6 @@
 //   recordCommandBuffer's vkCmdTraceRaysKHR :1971-1976 + rt_output_image running mean
 //       -> ptgs_trace_camera
 //   torus trace :1893-1900 / :2787-2794 -> ptgs_trace_torus
-// Largest BVH leaf (triangles). C3 at 64 spp (tools/ab_pt.py, interleaved): 1 -> 3 602, 2 -> 4 849,
-// 3 -> 4 836, 4 -> 4 463, 8 -> -10% Mrays/s; 3 keeps the tree a level shallower than 2 for the
-// traversal-stack budget of large meshes
-#ifndef PTGS_BVH_LEAF
-#define PTGS_BVH_LEAF 3
-#endif
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,10 +20,12 @@
 #include "../../include/ptgs/ptgs.h"
 #include "bvh.h"
 #include "bvh_gpu.h"
+#include "bvh_tries.h"
 #include "knn.h"
 #include "hostmath.h"
 #include "pt_launch.h"
 #include "pt_wavefront.h"
+#include "scene_flatten.h"
 #include "comm.h"
 #include "splat.h"
 #include "splat_backward.h"
@@ -85,55 +81,6 @@ struct ptgs_ctx {
 
 namespace {
 
-// 4-wide collapse whose worst-case traversal stack fits PTGS_STACK_TOTAL (LDS + overflow) with fan-out
-// `fan` (a 2-wide "collapse" needs the BVH2 depth, which the builders keep below PTGS_STACK)
-static bool collapse_fit(const std::vector<float>& n2, std::vector<float>& n4, uint32_t& num4, uint32_t& dep4, int fan,
-                         uint32_t& need) {
-  need = 0;
-  ptgs::collapse_bvh4(n2, n4, num4, need, dep4, fan);
-  return need < PTGS_STACK_TOTAL;
-}
-
-// (leaf size, fan-out) tried in this order until the tree's worst-case stack need fits PTGS_STACK_TOTAL:
-// a scene whose 3-triangle-leaf tree is too deep for a 4-wide collapse is rebuilt with 4-triangle
-// leaves before the fan-out is narrowed (a 2-wide fallback traced C5 at 1.38 Grays/s, the
-// 4-triangle-leaf 4-wide tree at ~2.1; with the stack overflow C5 keeps 3-triangle leaves: need 40)
-// Each try also carries the SAH build's depth budget (bvh.cpp: past it, balanced splits).
-struct BvhTry {
-  int leaf, fan;
-  uint32_t depth;
-};
-static const BvhTry kBvhTriesDefault[] = {{PTGS_BVH_LEAF, 4, PTGS_STACK - 1}, {PTGS_BVH_LEAF + 1, 4, PTGS_STACK - 1},
-                                          {PTGS_BVH_LEAF, 3, PTGS_STACK - 1}, {PTGS_BVH_LEAF, 2, PTGS_STACK - 1}};
-// PTGS_BVH_TRIES="leaf:fan:depth,..." replaces the list (A/B of tree shapes: tools/ab_pt.py AB_SCENE=c5)
-static std::vector<BvhTry> bvh_tries() {
-  std::vector<BvhTry> v;
-  if (const char* e = getenv("PTGS_BVH_TRIES")) {
-    for (const char* p = e; *p;) {
-      int l = 0, f = 0;
-      unsigned d = 0;
-      if (sscanf(p, "%d:%d:%u", &l, &f, &d) == 3 && l >= 1 && l <= 16 && f >= 2 && f <= 4 && d >= 1 && d < PTGS_STACK)
-        v.push_back({l, f, d});
-      while (*p && *p != ',') ++p;
-      if (*p == ',') ++p;
-    }
-  }
-  if (v.empty()) v.assign(std::begin(kBvhTriesDefault), std::end(kBvhTriesDefault));
-  return v;
-}
-// 4-wide nodes the traversal can address (PTGS_BVH_NODE_LIMIT lowers it: the guard's GPU test)
-static uint32_t bvh_node_limit() {
-  const uint32_t hw = 0x7fffffffu / 128u;
-  const char* e = getenv("PTGS_BVH_NODE_LIMIT");
-  const unsigned long v = e ? strtoul(e, nullptr, 10) : 0ul;
-  return v && v < hw ? (uint32_t)v : hw;
-}
-static void bvh_log(const char* how, int leaf, int fan, uint32_t budget, uint32_t depth, uint32_t need) {
-  if (getenv("PTGS_BVH_LOG"))
-    fprintf(stderr, "[ptgs] %s tree: leaf %d fan %d depth budget %u -> depth %u, stack need %u%s\n", how, leaf, fan,
-            budget, depth, need, need >= PTGS_STACK ? (need < PTGS_STACK_TOTAL ? " (DEEP)" : " (does not fit)") : "");
-}
-
 int fail(ptgs_ctx* c, int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
@@ -188,6 +135,245 @@ int fill_cam(ptgs_ctx* c, const ptgs_ubo* ubo, CamParams& cp) {
   cp.use_lod = ubo->use_lod;
   cp.lod_factor = ubo->lod_factor;
   return PTGS_OK;
+}
+
+// ---- scene upload: the three BVH builders, run under run_bvh_tries (bvh_tries.h), and the stages ----
+
+void bvh_log(const char* how, const BvhTry& t, uint32_t depth, uint32_t need) {
+  if (getenv("PTGS_BVH_LOG"))
+    fprintf(stderr, "[ptgs] %s tree: leaf %d fan %d depth budget %u -> depth %u, stack need %u%s\n", how, t.leaf, t.fan,
+            t.depth, depth, need, need >= PTGS_STACK ? (need < PTGS_STACK_TOTAL ? " (DEEP)" : " (does not fit)") : "");
+}
+
+double ms_between(std::chrono::steady_clock::time_point t0, std::chrono::steady_clock::time_point t1) {
+  return std::chrono::duration<double, std::milli>(t1 - t0).count();
+}
+
+// bytes of a triangle on the device: its record (3 float4, bvh.h) and its flag word
+constexpr size_t kTriDeviceBytes = 3 * sizeof(float4) + sizeof(uint32_t);
+
+// The host binned-SAH build (bvh.cpp). A BVH2 as deep as the LDS stack ends the tries: a 2-wide "collapse"
+// needs the BVH2's depth, so no fan-out would fit it.
+struct HostSahBuilder {
+  const std::vector<BuildTri>& tris;
+  BvhOut bvh;             // the latest BVH2; its tris / tri_flags are the records of every collapse of it
+  std::vector<float> n4;  // the latest collapse
+  uint32_t num4 = 0;
+  BvhStep build(int leaf, uint32_t depth, uint32_t stack_lds) {
+    build_bvh(tris, leaf, depth, bvh);
+    return bvh.depth >= stack_lds ? BvhStep::TooDeep : BvhStep::Ok;
+  }
+  BvhStep collapse(int fan, uint32_t& need, uint32_t& depth4) {
+    need = 0;
+    collapse_bvh4(bvh.nodes, n4, num4, need, depth4, fan);
+    return BvhStep::Ok;
+  }
+};
+
+// What a GPU builder holds on the device: the latest BVH2 with its triangle records, and the latest
+// collapse. All of it is freed with the builder unless hand_over() gave the tree to the scene; a build that
+// returned hipErrorNotSupported with `g` filled (bvh_gpu.h) is freed the same way.
+struct GpuTree {
+  GpuBvh g;
+  float4* n4 = nullptr;
+  uint32_t num4 = 0;
+  float ms = 0.0f;               // the builds' device time + the host-clock span of each collapse
+  hipError_t err = hipSuccess;   // the latest step's
+  GpuTree() = default;
+  GpuTree(const GpuTree&) = delete;
+  GpuTree& operator=(const GpuTree&) = delete;
+  ~GpuTree() {
+    release_bvh2();
+    (void)hipFree(n4);
+  }
+  void release_bvh2() {
+    (void)hipFree(g.nodes);
+    (void)hipFree(g.tris);
+    (void)hipFree(g.tri_flags);
+    g = GpuBvh{};
+  }
+  BvhStep step(hipError_t e) {
+    err = e;
+    return e == hipSuccess ? BvhStep::Ok : e == hipErrorNotSupported ? BvhStep::NotSupported : BvhStep::Error;
+  }
+  BvhStep collapse(int fan, uint32_t& need, uint32_t& depth4) {
+    const auto t0 = std::chrono::steady_clock::now();
+    (void)hipFree(n4);
+    n4 = nullptr;
+    const hipError_t e = collapse_bvh4_gpu(g.nodes, g.num_nodes, fan, &n4, &num4, &need, &depth4);
+    ms += (float)ms_between(t0, std::chrono::steady_clock::now());  // build_ms includes it
+    return step(e);
+  }
+  // the collapsed nodes and the triangle records become the scene's; the BVH2's nodes are done with
+  void hand_over(std::vector<void*>& allocs, DevScene& s) {
+    (void)hipFree(g.nodes);
+    for (void* p : {(void*)n4, (void*)g.tris, (void*)g.tri_flags}) allocs.push_back(p);
+    s.nodes = n4;
+    s.tris = g.tris;
+    s.tri_flags = g.tri_flags;
+    n4 = nullptr;
+    g = GpuBvh{};
+  }
+};
+// the GPU binned-SAH build (bvh_sah_gpu.hip): the host builder's trees
+struct GpuSahBuilder : GpuTree {
+  static constexpr uint32_t kId = PTGS_BUILDER_GPU_SAH;
+  const std::vector<BuildTri>& tris;
+  explicit GpuSahBuilder(const std::vector<BuildTri>& t) : tris(t) {}
+  BvhStep build(int leaf, uint32_t depth, uint32_t) {
+    release_bvh2();
+    float bms = 0.0f;
+    const hipError_t e = build_bvh_sah_gpu(tris, leaf, depth, g, &bms);
+    ms += bms;
+    return step(e);
+  }
+  uint32_t max_leaf() const { return g.max_leaf; }
+};
+// the GPU LBVH (bvh_gpu.hip): fixed leaves of up to 4 triangles, one build (lbvh_bvh_tries)
+struct GpuLbvhBuilder : GpuTree {
+  static constexpr uint32_t kId = PTGS_BUILDER_GPU_LBVH;
+  const std::vector<BuildTri>& tris;
+  explicit GpuLbvhBuilder(const std::vector<BuildTri>& t) : tris(t) {}
+  BvhStep build(int, uint32_t depth, uint32_t) {
+    release_bvh2();
+    float bms = 0.0f;
+    const hipError_t e = build_bvh_gpu(tris, depth, g, &bms);
+    ms += bms;
+    return step(e);
+  }
+  uint32_t max_leaf() const { return 4u; }
+};
+
+void publish_tree(ptgs_ctx* c, DevScene& s, uint32_t builder, const BvhTriesResult& r, uint32_t num4, uint32_t max_leaf,
+                  double build_ms) {
+  s.deep_stack = r.need >= PTGS_STACK ? 1 : 0;
+  c->info.num_bvh_nodes = num4;
+  c->info.bvh_depth = r.depth4;
+  c->info.max_leaf_size = max_leaf;
+  c->info.build_ms = build_ms;
+  c->build = ptgs_scene_build{builder, (uint32_t)r.kept.leaf, (uint32_t)r.kept.fan, r.kept.depth, r.need,
+                              (uint32_t)s.deep_stack};
+}
+
+// A tree of one of the GPU builders. *built stays false, with PTGS_OK, when the builder does not support the
+// input or none of its trees fits the stack: the host builds then (whatever the builder held goes with it).
+template <class Builder>
+int build_tree_gpu(ptgs_ctx* c, const std::vector<BuildTri>& tris, const std::vector<BvhTry>& tries, DevScene& s,
+                   bool* built) {
+  Builder b(tris);
+  const BvhTriesResult r =
+      run_bvh_tries(b, tries, PTGS_STACK, PTGS_STACK_TOTAL,
+                    [](const BvhTry& t, uint32_t depth4, uint32_t need) { bvh_log("GPU", t, depth4, need); });
+  if (r.fit == BvhFit::Error) return fail(c, PTGS_EHIP, "GPU BVH build: %s", hipGetErrorString(b.err));
+  if (r.fit != BvhFit::Fits) return PTGS_OK;
+  publish_tree(c, s, Builder::kId, r, b.num4, b.max_leaf(), b.ms);
+  c->info.device_bytes += (size_t)b.num4 * PTGS_NODE4_BYTES + tris.size() * kTriDeviceBytes;
+  b.hand_over(c->scene_allocs, s);
+  *built = true;
+  return PTGS_OK;
+}
+
+// The host's tree; host_n4 gets its final 4-wide nodes (upload_traversal_nodes reads them).
+int build_tree_host(ptgs_ctx* c, const std::vector<BuildTri>& tris, DevScene& s, std::vector<float>& host_n4) {
+  const auto t0 = std::chrono::steady_clock::now();
+  HostSahBuilder b{tris};
+  const BvhTriesResult r =
+      run_bvh_tries(b, parse_bvh_tries(getenv("PTGS_BVH_TRIES"), PTGS_STACK), PTGS_STACK, PTGS_STACK_TOTAL,
+                    [](const BvhTry& t, uint32_t depth4, uint32_t need) { bvh_log("host", t, depth4, need); });
+  const auto t1 = std::chrono::steady_clock::now();
+  if (r.fit != BvhFit::Fits) return fail(c, PTGS_ERANGE, "BVH depth %u exceeds the traversal stack", b.bvh.depth);
+  int rc;
+  if ((rc = upload(c, (const float4*)b.n4.data(), b.n4.size() / 4, &s.nodes))) return rc;
+  if ((rc = upload(c, (const float4*)b.bvh.tris.data(), b.bvh.tris.size() / 4, &s.tris))) return rc;
+  if ((rc = upload(c, b.bvh.tri_flags.data(), b.bvh.tri_flags.size(), &s.tri_flags))) return rc;
+  publish_tree(c, s, PTGS_BUILDER_HOST_SAH, r, b.num4, b.bvh.max_leaf, ms_between(t0, t1));
+  host_n4.swap(b.n4);
+  return PTGS_OK;
+}
+
+// The traversal reads 4-wide nodes through a buffer descriptor with 32-bit byte offsets (node << 7,
+// num_records 0x7fffffff: pt_device.h box4): nodes past 2 GiB would read as zeros (no boxes, child
+// link 0) without a fault. Such a tree (~16.7M nodes, some 50M triangles) is refused here.
+int check_node_window(ptgs_ctx* c) {
+  const uint32_t limit = bvh_node_limit(getenv("PTGS_BVH_NODE_LIMIT"));
+  if (c->info.num_bvh_nodes > limit)
+    return fail(c, PTGS_ERANGE, "BVH of %u 4-wide nodes exceeds the traversal's 2 GiB node window (%u nodes)",
+                c->info.num_bvh_nodes, limit);
+  return PTGS_OK;
+}
+
+// The megakernel's traversal reads a compact 64-B copy of the final nodes (bvh.h make_traversal_nodes; one
+// conversion for the host SAH, GPU SAH and LBVH trees: a GPU-built tree is read back for it). Their links
+// are re-encoded into the fewest bits this tree needs, so that a stack entry of the closest-hit walk
+// carries the child's entry distance in the bits left (bvh.h stack_layout, stack_key.h).
+// PTGS_PT_STACK_KEY_BITS forces the key's width (tests: 0 = never cull).
+int upload_traversal_nodes(ptgs_ctx* c, std::vector<float>& host_n4, DevScene& s) {
+  const size_t nf = (size_t)c->info.num_bvh_nodes * 32;
+  if (host_n4.size() != nf) {
+    host_n4.resize(nf);
+    HIPCHK(c, hipMemcpy(host_n4.data(), s.nodes, nf * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  int force = -1;
+  if (const char* e = getenv("PTGS_PT_STACK_KEY_BITS")) force = std::max(0, atoi(e));
+  std::vector<uint32_t> n64;
+  StackLayout sl;
+  if (!make_traversal_nodes(host_n4.data(), c->info.num_bvh_nodes, force, n64, sl))
+    return fail(c, PTGS_ERANGE, "BVH node extents beyond the compact nodes' step range (2^-100 .. 2^100)");
+  s.stk_key_mask = sl.key_mask;
+  s.leaf_shift = sl.leaf_shift;
+  s.leaf_start_mask = sl.leaf_start_mask;
+  if (getenv("PTGS_BVH_LOG"))
+    fprintf(stderr, "[ptgs] stack word:%u link bits, %u key bits (mask %08x), leaf shift %u\n", sl.ref_bits, sl.key_bits,
+            sl.key_mask, sl.leaf_shift);
+  return upload(c, (const uint4*)n64.data(), n64.size() / 4, &s.nodes64);
+}
+
+// the description's arrays, the hit records and the texture pool
+int upload_scene_arrays(ptgs_ctx* c, const ptgs_scene_desc* d, const FlatScene& flat, const TexturePool& texpool,
+                        DevScene& s) {
+  int rc;
+  // a zero vertex/index count still needs valid (never dereferenced) pointers
+  ptgs_vertex dummy_v{};
+  uint32_t dummy_i = 0;
+  ptgs_mesh_info dummy_m{};
+  if ((rc = upload(c, d->num_vertices ? d->vertices : &dummy_v, d->num_vertices ? d->num_vertices : 1, &s.vertices))) return rc;
+  if ((rc = upload(c, d->num_indices ? d->indices : &dummy_i, d->num_indices ? d->num_indices : 1, &s.indices))) return rc;
+  if ((rc = upload(c, d->num_meshes ? d->meshes : &dummy_m, d->num_meshes ? d->num_meshes : 1, &s.meshes))) return rc;
+  if ((rc = upload(c, d->materials, d->num_materials, &s.materials))) return rc;
+  const std::vector<uint32_t>& hitrec = flat.hitrec;
+  const uint32_t zero4[4] = {0, 0, 0, 0};
+  if ((rc = upload(c, (const uint4*)(hitrec.empty() ? zero4 : hitrec.data()), hitrec.empty() ? 1 : hitrec.size() / 4,
+                   &s.hitrec)))
+    return rc;
+  if ((rc = upload(c, d->light_triangles, d->num_light_triangles, &s.light_tris))) return rc;
+  if ((rc = upload(c, d->light_cdf, d->num_light_cdf, &s.light_cdf))) return rc;
+  if ((rc = upload(c, d->punctual_lights, d->num_punctual_lights, &s.plights))) return rc;
+  if ((rc = upload(c, d->punctual_cdf, d->num_punctual_cdf, &s.pcdf))) return rc;
+  const size_t bn = d->blue_noise_size;
+  if ((rc = upload(c, (const float4*)d->blue_noise_rgba32f, bn * bn, &s.blue_noise))) return rc;
+  if ((rc = upload(c, texpool.texels.data(), texpool.texels.size(), &s.tex.texels))) return rc;
+  if ((rc = upload(c, texpool.info.data(), texpool.info.size(), &s.tex.info))) return rc;
+  return upload(c, texpool.lut.data(), texpool.lut.size(), &s.tex.lut);
+}
+
+// the scalars of the device scene, and the scene becomes the context's
+void publish_scene(ptgs_ctx* c, const ptgs_scene_desc* d, const FlatScene& flat, DevScene& s) {
+  s.tex.count = d->num_textures;
+  s.uses_textures = 0;
+  for (uint32_t i = 0; i < d->num_materials; ++i) {
+    const ptgs_material& m = d->materials[i];
+    if (m.albedo_texture_index > 0 || m.normal_texture_index > 0 || m.metallic_roughness_texture_index > 0 ||
+        m.emissive_texture_index > 0 || m.clearcoat_texture_index > 0 || m.clearcoat_roughness_texture_index > 0 ||
+        m.sg_id > 0)
+      s.uses_textures = 1;
+  }
+  s.num_light_cdf = d->num_light_cdf;
+  s.num_plights = d->num_punctual_lights;
+  s.bn_size = (int32_t)d->blue_noise_size;
+  s.has_transparent = flat.has_transparent ? 1 : 0;
+  c->dsc = s;
+  c->has_scene = true;
+  c->info.num_triangles = (uint32_t)flat.tris.size();
 }
 
 }  // namespace
@@ -329,257 +515,36 @@ const char* ptgs_last_error(const ptgs_ctx* c) { return c ? c->err.c_str() : "nu
 int ptgs_scene_upload(ptgs_ctx* c, const ptgs_scene_desc* d) {
   if (!c || !d) return PTGS_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
-  if (!d->vertices && d->num_vertices) return fail(c, PTGS_EINVAL, "vertices is null");
-  if (!d->indices && d->num_indices) return fail(c, PTGS_EINVAL, "indices is null");
-  if (d->num_meshes && (!d->meshes || !d->mesh_index_count)) return fail(c, PTGS_EINVAL, "meshes is null");
-  if (!d->materials || d->num_materials == 0) return fail(c, PTGS_EINVAL, "at least one material is required");
-  if (!d->light_triangles || !d->light_cdf || d->num_light_cdf == 0 || d->num_light_triangles == 0)
-    return fail(c, PTGS_EINVAL, "light triangle / CDF buffers must hold >= 1 entry (engine.cpp:1766-1769 dummy)");
-  if (!d->punctual_lights || !d->punctual_cdf || d->num_punctual_lights == 0 || d->num_punctual_cdf == 0)
-    return fail(c, PTGS_EINVAL, "punctual light / CDF buffers must hold >= 1 entry (engine.cpp:1795-1797 dummy)");
-  uint32_t bn = d->blue_noise_size;
-  if (!d->blue_noise_rgba32f || bn == 0 || (bn & (bn - 1)) != 0)
-    return fail(c, PTGS_EINVAL, "blue noise must be a power-of-two square RGBA32F texture");
-  if (d->num_textures && !d->textures) return fail(c, PTGS_EINVAL, "textures is null");
+  int rc;
+  std::string msg;
+  if ((rc = validate_scene_desc(d, msg))) return fail(c, rc, "%s", msg.c_str());
   TexturePool texpool;
-  {
-    std::string terr;
-    if (!build_texture_pool(d->textures, d->num_textures, texpool, terr)) return fail(c, PTGS_EINVAL, "%s", terr.c_str());
-    if (texpool.texels.size() >= (1ull << 32)) return fail(c, PTGS_ERANGE, "texture pool exceeds 2^32 texels");
-  }
-
-  // gather triangles in flattening order (gid), skipping meshes with < 3 indices (engine.cpp:545-547)
-  std::vector<BuildTri> tris;
-  std::vector<uint32_t> hitrec;  // per gid: global vertex indices + material (closest_hit's one fetch)
-  bool has_transparent = false;
-  for (uint32_t m = 0; m < d->num_meshes; ++m) {
-    const ptgs_mesh_info& mi = d->meshes[m];
-    uint32_t cnt = d->mesh_index_count[m];
-    if (cnt < 3) continue;
-    if (mi.material_index >= d->num_materials) return fail(c, PTGS_EINVAL, "mesh %u: material %u out of range", m, mi.material_index);
-    if ((uint64_t)mi.index_offset + cnt > d->num_indices) return fail(c, PTGS_EINVAL, "mesh %u: index range out of bounds", m);
-    const ptgs_material& mat = d->materials[mi.material_index];
-    uint32_t flags = (mat.pad > 0.5f) ? 1u : 0u;  // non-opaque geometry (engine.cpp:562-567)
-    has_transparent |= flags != 0;
-    for (uint32_t p = 0; p < cnt / 3; ++p) {
-      BuildTri t;
-      for (int k = 0; k < 3; ++k) {
-        uint32_t vi = d->indices[mi.index_offset + 3 * p + k] + mi.vertex_offset;
-        if (vi >= d->num_vertices) return fail(c, PTGS_EINVAL, "mesh %u prim %u: vertex %u out of range", m, p, vi);
-        float* dst = k == 0 ? t.v0 : (k == 1 ? t.v1 : t.v2);
-        std::memcpy(dst, d->vertices[vi].pos, 12);
-        hitrec.push_back(vi);
-      }
-      hitrec.push_back(mi.material_index);
-      t.mesh = m; t.prim = p; t.gid = (uint32_t)tris.size(); t.flags = flags;
-      tris.push_back(t);
-    }
-  }
-  if (tris.size() >= (1u << 27)) return fail(c, PTGS_ERANGE, "too many triangles (%zu)", tris.size());
-  if (d->num_punctual_cdf < d->num_punctual_lights)
-    return fail(c, PTGS_EINVAL, "punctual CDF shorter than the light list (binary search runs over the light count)");
-  for (uint32_t i = 0; i < d->num_light_cdf; ++i)
-    if (d->light_cdf[i].triangle_index >= d->num_light_triangles)
-      return fail(c, PTGS_EINVAL, "light CDF entry %u: triangle %u out of range", i, d->light_cdf[i].triangle_index);
-  for (uint32_t i = 0; i < d->num_light_triangles; ++i) {
-    const ptgs_light_triangle& lt = d->light_triangles[i];
-    if (d->num_vertices == 0 || lt.v0 >= d->num_vertices || lt.v1 >= d->num_vertices || lt.v2 >= d->num_vertices) {
-      if (d->num_light_triangles == 1 && lt.v0 == 0 && lt.v1 == 0 && lt.v2 == 0) continue;  // dummy
-      return fail(c, PTGS_EINVAL, "light triangle %u references a vertex out of range", i);
-    }
-  }
+  if (!build_texture_pool(d->textures, d->num_textures, texpool, msg)) return fail(c, PTGS_EINVAL, "%s", msg.c_str());
+  if (texpool.texels.size() >= (1ull << 32)) return fail(c, PTGS_ERANGE, "texture pool exceeds 2^32 texels");
+  FlatScene flat;
+  if ((rc = flatten_scene(d, flat, msg))) return fail(c, rc, "%s", msg.c_str());
 
   free_scene(c);
   c->info = ptgs_scene_info{};
   c->build = ptgs_scene_build{};
   DevScene s{};
-  int rc;
-  // BVH: the host binned-SAH build (default), or with PTGS_FLAG_GPU_BVH the GPU LBVH (bvh_gpu.hip),
-  // falling back to the host build when the LBVH is deeper than the traversal stack
+  // BVH: the host binned-SAH build (default), or with PTGS_FLAG_GPU_BVH one of the GPU builders (the SAH
+  // build with the host's tries, or with PTGS_FLAG_GPU_LBVH the LBVH), falling back to the host build when
+  // the GPU builder does not support the input or none of its trees fits the traversal stack
   bool built = false;
-  std::vector<float> host_n4;  // the final 4-wide nodes when the host built them (nodes64 below)
-  if ((c->flags & PTGS_FLAG_GPU_BVH) && tris.size() >= 16) {
-    GpuBvh g;
-    float ms = 0.0f;
-    hipError_t e = hipSuccess;
-    // (leaf, fan) as the host path (kBvhTries); the LBVH has fixed leaves: fan-out 4, 3, 2
-    const bool lbvh = (c->flags & PTGS_FLAG_GPU_LBVH) != 0;
-    const std::vector<BvhTry> tl = bvh_tries();
-    const int tries = lbvh ? 3 : (int)tl.size();
-    int built_leaf = -1;
-    uint32_t built_depth = 0;
-    float4* n4 = nullptr;
-    uint32_t num4 = 0, need = PTGS_STACK_TOTAL, dep4 = 0;
-    BvhTry kept{0, 0, 0};  // the try whose collapse ran last
-    for (int k = 0; k < tries; ++k) {
-      const int leaf = lbvh ? 0 : tl[k].leaf, fan = lbvh ? 4 - k : tl[k].fan;
-      const uint32_t depth = lbvh ? PTGS_STACK - 1 : tl[k].depth;
-      if (leaf != built_leaf || depth != built_depth) {  // (re)build the BVH2
-        if (built_leaf >= 0) {
-          (void)hipFree(g.nodes);
-          (void)hipFree(g.tris);
-          (void)hipFree(g.tri_flags);
-          g = GpuBvh{};
-        }
-        float bms = 0.0f;
-        e = lbvh ? build_bvh_gpu(tris, PTGS_STACK - 1, g, &bms) : build_bvh_sah_gpu(tris, leaf, depth, g, &bms);
-        ms += bms;
-        if (e != hipSuccess) break;
-        built_leaf = leaf;
-        built_depth = depth;
-      }
-      // 4-wide collapse on the GPU
-      auto t0 = std::chrono::steady_clock::now();
-      (void)hipFree(n4);
-      n4 = nullptr;
-      e = collapse_bvh4_gpu(g.nodes, g.num_nodes, fan, &n4, &num4, &need, &dep4);
-      auto t1 = std::chrono::steady_clock::now();
-      if (e == hipSuccess) bvh_log("GPU", leaf, fan, depth, dep4, need);
-      kept = BvhTry{leaf, fan, depth};
-      ms += (float)std::chrono::duration<double, std::milli>(t1 - t0).count();  // build_ms includes it
-      if (e != hipSuccess || need < PTGS_STACK_TOTAL) break;
-    }
-    if (e == hipSuccess && need >= PTGS_STACK_TOTAL) e = hipErrorNotSupported;
-    if (e == hipSuccess || e == hipErrorNotSupported) {
-      (void)hipFree(g.nodes);
-      g.nodes = n4;
-      g.num_nodes = num4;
-      g.depth = dep4;
-    } else {
-      (void)hipFree(n4);
-    }
-    if (e == hipSuccess) {
-      for (void* p : {(void*)g.nodes, (void*)g.tris, (void*)g.tri_flags}) c->scene_allocs.push_back(p);
-      s.nodes = g.nodes;
-      s.tris = g.tris;
-      s.tri_flags = g.tri_flags;
-      s.deep_stack = need >= PTGS_STACK ? 1 : 0;
-      c->info.num_bvh_nodes = g.num_nodes;
-      c->info.bvh_depth = g.depth;
-      c->info.max_leaf_size = (c->flags & PTGS_FLAG_GPU_LBVH) ? 4u : g.max_leaf;
-      c->info.build_ms = ms;
-      c->info.device_bytes += (size_t)g.num_nodes * 128 + tris.size() * 52;
-      c->build = ptgs_scene_build{lbvh ? PTGS_BUILDER_GPU_LBVH : PTGS_BUILDER_GPU_SAH, (uint32_t)kept.leaf,
-                                  (uint32_t)kept.fan, kept.depth, need, (uint32_t)s.deep_stack};
-      built = true;
-    } else if (e == hipErrorNotSupported) {
-      (void)hipFree(g.nodes);
-      (void)hipFree(g.tris);
-      (void)hipFree(g.tri_flags);
-    } else {
-      (void)hipFree(g.nodes);
-      (void)hipFree(g.tris);
-      (void)hipFree(g.tri_flags);
-      return fail(c, PTGS_EHIP, "GPU BVH build: %s", hipGetErrorString(e));
-    }
+  if ((c->flags & PTGS_FLAG_GPU_BVH) && flat.tris.size() >= 16) {
+    rc = (c->flags & PTGS_FLAG_GPU_LBVH)
+             ? build_tree_gpu<GpuLbvhBuilder>(c, flat.tris, lbvh_bvh_tries(PTGS_STACK), s, &built)
+             : build_tree_gpu<GpuSahBuilder>(c, flat.tris, parse_bvh_tries(getenv("PTGS_BVH_TRIES"), PTGS_STACK), s,
+                                             &built);
+    if (rc) return rc;
   }
-  if (!built) {
-    auto t0 = std::chrono::steady_clock::now();
-    BvhOut bvh;
-    std::vector<float> n4;
-    uint32_t num4 = 0, dep4 = 0, need = PTGS_STACK_TOTAL;
-    int built_leaf = -1;
-    bool fits = false;
-    uint32_t built_depth = 0;
-    BvhTry kept{0, 0, 0};
-    for (const BvhTry& tr : bvh_tries()) {
-      if (tr.leaf != built_leaf || tr.depth != built_depth) {
-        build_bvh(tris, tr.leaf, tr.depth, bvh);
-        built_leaf = tr.leaf;
-        built_depth = tr.depth;
-        if (bvh.depth >= PTGS_STACK) return fail(c, PTGS_ERANGE, "BVH depth %u exceeds the traversal stack", bvh.depth);
-      }
-      fits = collapse_fit(bvh.nodes, n4, num4, dep4, tr.fan, need);
-      bvh_log("host", tr.leaf, tr.fan, tr.depth, dep4, need);
-      kept = tr;
-      if (fits) break;
-    }
-    auto t1 = std::chrono::steady_clock::now();
-    if (!fits) return fail(c, PTGS_ERANGE, "BVH depth %u exceeds the traversal stack", bvh.depth);
-    s.deep_stack = need >= PTGS_STACK ? 1 : 0;
-    if ((rc = upload(c, (const float4*)n4.data(), n4.size() / 4, &s.nodes))) return rc;
-    host_n4.swap(n4);
-    bvh.num_nodes = num4;
-    bvh.depth = dep4;
-    if ((rc = upload(c, (const float4*)bvh.tris.data(), bvh.tris.size() / 4, &s.tris))) return rc;
-    if ((rc = upload(c, bvh.tri_flags.data(), bvh.tri_flags.size(), &s.tri_flags))) return rc;
-    c->info.num_bvh_nodes = bvh.num_nodes;
-    c->info.bvh_depth = bvh.depth;
-    c->info.max_leaf_size = bvh.max_leaf;
-    c->info.build_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    c->build = ptgs_scene_build{PTGS_BUILDER_HOST_SAH, (uint32_t)kept.leaf, (uint32_t)kept.fan, kept.depth, need,
-                                (uint32_t)s.deep_stack};
-  }
-  // The traversal reads 4-wide nodes through a buffer descriptor with 32-bit byte offsets (node << 7,
-  // num_records 0x7fffffff: pt_device.h box4): nodes past 2 GiB would read as zeros (no boxes, child
-  // link 0) without a fault. Such a tree (~16.7M nodes, some 50M triangles) is refused here.
-  if (c->info.num_bvh_nodes > bvh_node_limit())
-    return fail(c, PTGS_ERANGE, "BVH of %u 4-wide nodes exceeds the traversal's 2 GiB node window (%u nodes)",
-                c->info.num_bvh_nodes, bvh_node_limit());
-  // The megakernel's traversal reads a compact 64-B copy of the final nodes (bvh.h quantize_bvh4; one
-  // conversion for the host SAH, GPU SAH and LBVH trees: a GPU-built tree is read back for it).
-  {
-    const size_t nf = (size_t)c->info.num_bvh_nodes * 32;
-    if (host_n4.size() != nf) {
-      host_n4.resize(nf);
-      HIPCHK(c, hipMemcpy(host_n4.data(), s.nodes, nf * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    std::vector<uint32_t> n64;
-    if (!quantize_bvh4(host_n4.data(), c->info.num_bvh_nodes, n64))
-      return fail(c, PTGS_ERANGE, "BVH node extents beyond the compact nodes' step range (2^-100 .. 2^100)");
-    // Their links are re-encoded into the fewest bits this tree needs, so that a stack entry of the
-    // closest-hit walk carries the child's entry distance in the bits left (bvh.h stack_layout,
-    // stack_key.h). PTGS_PT_STACK_KEY_BITS forces the key's width (tests: 0 = never cull).
-    int force = -1;
-    if (const char* e = getenv("PTGS_PT_STACK_KEY_BITS")) force = std::max(0, atoi(e));
-    const StackLayout sl = stack_layout(host_n4.data(), c->info.num_bvh_nodes, force);
-    pack_links64(n64, c->info.num_bvh_nodes, sl);
-    s.stk_key_mask = sl.key_mask;
-    s.leaf_shift = sl.leaf_shift;
-    s.leaf_start_mask = sl.leaf_start_mask;
-    if (getenv("PTGS_BVH_LOG"))
-      fprintf(stderr, "[ptgs] stack word:%u link bits, %u key bits (mask %08x), leaf shift %u\n", sl.ref_bits, sl.key_bits,
-              sl.key_mask, sl.leaf_shift);
-    if ((rc = upload(c, (const uint4*)n64.data(), n64.size() / 4, &s.nodes64))) return rc;
-  }
-  // a zero vertex/index count still needs valid (never dereferenced) pointers
-  ptgs_vertex dummy_v{};
-  uint32_t dummy_i = 0;
-  ptgs_mesh_info dummy_m{};
-  if ((rc = upload(c, d->num_vertices ? d->vertices : &dummy_v, d->num_vertices ? d->num_vertices : 1, &s.vertices))) return rc;
-  if ((rc = upload(c, d->num_indices ? d->indices : &dummy_i, d->num_indices ? d->num_indices : 1, &s.indices))) return rc;
-  if ((rc = upload(c, d->num_meshes ? d->meshes : &dummy_m, d->num_meshes ? d->num_meshes : 1, &s.meshes))) return rc;
-  if ((rc = upload(c, d->materials, d->num_materials, &s.materials))) return rc;
-  {
-    const uint32_t zero4[4] = {0, 0, 0, 0};
-    if ((rc = upload(c, (const uint4*)(hitrec.empty() ? zero4 : hitrec.data()), hitrec.empty() ? 1 : hitrec.size() / 4,
-                     &s.hitrec)))
-      return rc;
-  }
-  if ((rc = upload(c, d->light_triangles, d->num_light_triangles, &s.light_tris))) return rc;
-  if ((rc = upload(c, d->light_cdf, d->num_light_cdf, &s.light_cdf))) return rc;
-  if ((rc = upload(c, d->punctual_lights, d->num_punctual_lights, &s.plights))) return rc;
-  if ((rc = upload(c, d->punctual_cdf, d->num_punctual_cdf, &s.pcdf))) return rc;
-  if ((rc = upload(c, (const float4*)d->blue_noise_rgba32f, (size_t)bn * bn, &s.blue_noise))) return rc;
-  if ((rc = upload(c, texpool.texels.data(), texpool.texels.size(), &s.tex.texels))) return rc;
-  if ((rc = upload(c, texpool.info.data(), texpool.info.size(), &s.tex.info))) return rc;
-  if ((rc = upload(c, texpool.lut.data(), texpool.lut.size(), &s.tex.lut))) return rc;
-  s.tex.count = d->num_textures;
-  s.uses_textures = 0;
-  for (uint32_t i = 0; i < d->num_materials; ++i) {
-    const ptgs_material& m = d->materials[i];
-    if (m.albedo_texture_index > 0 || m.normal_texture_index > 0 || m.metallic_roughness_texture_index > 0 ||
-        m.emissive_texture_index > 0 || m.clearcoat_texture_index > 0 || m.clearcoat_roughness_texture_index > 0 ||
-        m.sg_id > 0)
-      s.uses_textures = 1;
-  }
-  s.num_light_cdf = d->num_light_cdf;
-  s.num_plights = d->num_punctual_lights;
-  s.bn_size = (int32_t)bn;
-  s.has_transparent = has_transparent ? 1 : 0;
-  c->dsc = s;
-  c->has_scene = true;
-  c->info.num_triangles = (uint32_t)tris.size();
+  std::vector<float> host_n4;  // the final 4-wide nodes when the host built them
+  if (!built && (rc = build_tree_host(c, flat.tris, s, host_n4))) return rc;
+  if ((rc = check_node_window(c))) return rc;
+  if ((rc = upload_traversal_nodes(c, host_n4, s))) return rc;
+  if ((rc = upload_scene_arrays(c, d, flat, texpool, s))) return rc;
+  publish_scene(c, d, flat, s);
   return PTGS_OK;
 }
 

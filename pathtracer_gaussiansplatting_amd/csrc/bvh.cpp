@@ -413,4 +413,12 @@ void pack_links64(std::vector<uint32_t>& n64, uint32_t num, const StackLayout& l
     }
 }
 
+bool make_traversal_nodes(const float* n4, uint32_t num, int force_key_bits, std::vector<uint32_t>& n64,
+                          StackLayout& layout) {
+  if (!quantize_bvh4(n4, num, n64)) return false;
+  layout = stack_layout(n4, num, force_key_bits);
+  pack_links64(n64, num, layout);
+  return true;
+}
+
 }  // namespace ptgs

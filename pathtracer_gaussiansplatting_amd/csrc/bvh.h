@@ -75,4 +75,9 @@ StackLayout stack_layout(const float* nodes4, uint32_t num_nodes, int force_key_
 // leaf_shift, the empty slots' 0 stays.
 void pack_links64(std::vector<uint32_t>& nodes64, uint32_t num_nodes, const StackLayout& layout);
 
+// What the megakernel's traversal reads, from the final 4-wide nodes of any builder: quantize_bvh4, then
+// stack_layout, then pack_links64. False when quantize_bvh4 refuses the tree (layout is then untouched).
+bool make_traversal_nodes(const float* nodes4, uint32_t num_nodes, int force_key_bits, std::vector<uint32_t>& nodes64,
+                          StackLayout& layout);
+
 }  // namespace ptgs

@@ -117,7 +117,7 @@ __device__ __forceinline__ void pt_lanes_flush(const PtLaneCounts& c) {
 // 39 x 256 x 4 B = 39 KiB per workgroup (+ 1 KiB of slot rings in the wavefront kernels: 4
 // workgroups = 16 waves per CU fill the 160 KiB LDS). Deeper entries, up to PTGS_STACK_TOTAL, go
 // to a per-work-item overflow: private (scratch) memory in the megakernel, a global column in the
-// wavefront kernels. A 4-wide node pushes up to 3 entries: the scene upload (api.cpp kBvhTries)
+// wavefront kernels. A 4-wide node pushes up to 3 entries: the scene upload (bvh_tries.h run_bvh_tries)
 // rebuilds with 4-triangle leaves, then caps the fan-out, only if the tree's worst-case stack need
 // exceeds PTGS_STACK_TOTAL. C3's 250k-triangle atrium needs 38 with 3-triangle leaves, C5's
 // 1M-triangle atrium 40 (tools/native/bvh_need.cpp): both keep 3-triangle leaves and 4-wide nodes.

@@ -4,7 +4,7 @@
 //   anyhit_walk_check <tris.bin> <leaf> <fan> <depth> <waves>
 //
 // tris.bin holds float32 triangles (9 floats each; an empty file: the empty tree). The program builds the
-// host tree as the scene upload does (build_bvh, collapse_bvh4, quantize_bvh4, stack_layout, pack_links64)
+// host tree as the scene upload does (build_bvh, collapse_bvh4, make_traversal_nodes)
 // and restates the walk as a 64-lane lockstep model: the lanes of a wave that are in a loop run its body
 // together and the loop ends when the last of them leaves, as the hardware's exec mask does it. The float
 // expressions are the kernel's (box4_q, tri_isect and leaf_any's folded form; -ffp-contract=off, explicit
@@ -361,12 +361,13 @@ int main(int argc, char** argv) {
     build_bvh(tris, leafsz, depth, bvh);
     uint32_t dep4 = 0;
     collapse_bvh4(bvh.nodes, tr.n4, tr.num, tr.need, dep4, fan);
-    if (!quantize_bvh4(tr.n4.data(), tr.num, tr.n64)) { printf("anyhit_walk_check: conversion refused\n"); return 1; }
     tr.tris.swap(bvh.tris);
     tr.flags.swap(bvh.tri_flags);
   }
-  tr.lay = stack_layout(tr.n4.data(), tr.num, -1);
-  pack_links64(tr.n64, tr.num, tr.lay);
+  if (!make_traversal_nodes(tr.n4.data(), tr.num, -1, tr.n64, tr.lay)) {
+    printf("anyhit_walk_check: conversion refused\n");
+    return 1;
+  }
   if (tr.num >= DONE) ++g_viol;  // no interior index reaches the sentinel
 
   const float ext[3] = {bhi[0] - blo[0], bhi[1] - blo[1], bhi[2] - blo[2]};

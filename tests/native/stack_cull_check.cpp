@@ -305,11 +305,12 @@ int main(int argc, char** argv) {
     build_bvh(tris, leafsz, depth, bvh);
     uint32_t need = 0, dep4 = 0;
     collapse_bvh4(bvh.nodes, tr.n4, tr.num, need, dep4, fan);
-    if (!quantize_bvh4(tr.n4.data(), tr.num, tr.n64)) { printf("stack_cull_check: conversion refused\n"); return 1; }
     tr.tris.swap(bvh.tris);
   }
-  tr.lay = stack_layout(tr.n4.data(), tr.num, -1);
-  pack_links64(tr.n64, tr.num, tr.lay);
+  if (!make_traversal_nodes(tr.n4.data(), tr.num, -1, tr.n64, tr.lay)) {
+    printf("stack_cull_check: conversion refused\n");
+    return 1;
+  }
   unsigned long long links = 0;
   g_viol += check_links(tr, links);
   if (tr.num == 0 && (tr.lay.ref_bits != 1u || tr.lay.key_bits != 31u || tr.lay.leaf_shift != 0u)) ++g_viol;

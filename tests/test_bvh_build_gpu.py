@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 W, H, SPP = 64, 48, 2
 AMBIENT = (0.3, 0.4, 0.5, 1.0)
 HOST, GPU_SAH, GPU_LBVH = 0, 1, 2
-DEFAULT_TRY = (3, 4, 38)  # api.cpp kBvhTriesDefault[0]
+DEFAULT_TRY = (3, 4, 38)  # bvh_tries.h default_bvh_tries()[0]
 
 _SCENES = {}
 _ORACLE = {}
