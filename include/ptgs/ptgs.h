@@ -40,7 +40,7 @@ extern "C" {
                              * ptgs_gaussian_grads), ptgs_gaussians_sh_colors_backward,
                              * ptgs_gaussians_activate_backward, ptgs_densify_accumulate,
                              * ptgs_gaussians_densify_plan, ptgs_gaussians_densify_apply (with their three
-                             * structs); ptgs_read_gaussian_ply in ptgs_host.h */
+                             * structs), ptgs_image_loss_l1_dssim; ptgs_read_gaussian_ply in ptgs_host.h */
 
 /* ---------------- error codes ---------------- */
 #define PTGS_OK 0
@@ -791,6 +791,36 @@ int ptgs_gaussians_densify_apply(ptgs_ctx* ctx, uint32_t n, uint32_t n_out, cons
                                  const float* noise, float* means_out, float* log_scales_out,
                                  const ptgs_densify_rows* rows, uint32_t n_rows, uint32_t* source_out,
                                  void* hip_stream);
+
+/* The 3DGS training loss (Kerbl et al.) of a rendered frame against a target, and its gradient:
+ *   loss = (1 - lambda) * l1 + lambda * (1 - ssim),   l1 = mean |a - b|,   ssim = mean m     (lambda = 0.2 in the paper)
+ * a = image_rgba32f [H, W, 4] as the rasterizer writes it, b = target [H, W, target_channels], target_channels
+ * 3 or 4; both contiguous device float32, values expected in roughly [0, 1] (NaN / Inf and HDR magnitudes are
+ * not handled). Only channels 0..2 take part; the means are over n = 3 W H values.
+ *   g[k] = exp(-(k - 5)^2 / (2 * 1.5^2)), k = 0..10, normalised to sum 1;  w = g (x) g
+ *   conv(x) = per-channel correlation with w, zero padding of 5 (missing pixels count as 0; no renormalisation)
+ *   mu1 = conv(a); mu2 = conv(b); s1 = conv(a a) - mu1^2; s2 = conv(b b) - mu2^2; s12 = conv(a b) - mu1 mu2
+ *   C1 = 0.01^2; C2 = 0.03^2; A = 2 mu1 mu2 + C1; B = 2 s12 + C2; Cc = mu1^2 + mu2^2 + C1; D = s1 + s2 + C2
+ *   m = A B / (Cc D)
+ *   dm/ds1 = -m / D;  dm/ds12 = 2 A / (Cc D)
+ *   dm/dmu1 = 2 mu2 B / (Cc D) - 2 mu1 m / Cc - 2 mu1 dm/ds1 - mu2 dm/ds12
+ *   G = conv(dm/dmu1) + 2 a conv(dm/ds1) + b conv(dm/ds12)
+ *   dL/da = grad_scale * [ (1 - lambda) / n * sign(a - b) - lambda / n * G ],   sign(0) = 0
+ * loss_out: device float[4] = (loss, l1, ssim, 0). dL_dimage_rgba32f: device [H, W, 4], every element
+ * overwritten (alpha with 0), or NULL: only the terms are computed (bit for bit the terms of a call with the
+ * gradient). The arithmetic is f32 with explicit FMA, separable (11 + 11 taps), the sums of the two means in
+ * f64; the contract is a tolerance against a float64 evaluation of the formulas above, not bit-exactness
+ * against a restatement. There are no float atomics and every sum has a fixed order: two calls on the same
+ * inputs give the same bits. Stream-ordered with no host wait; the partial maps (36 bytes per pixel) live in a
+ * workspace of the context that grows on demand (a growing call frees the old one, which may synchronise the
+ * device), so the calls of one context must be ordered on their streams. Any 4-byte-aligned base is accepted
+ * (16-byte accesses where the bases allow).
+ * PTGS_EINVAL (message in ptgs_last_error, nothing enqueued): a null ctx, image, target or loss_out; width or
+ * height 0 or above 16384; target_channels not 3 or 4; lambda NaN or outside [0, 1]; grad_scale not finite;
+ * dL_dimage overlapping image or target; loss_out or dL_dimage not a device pointer. */
+int ptgs_image_loss_l1_dssim(ptgs_ctx* ctx, const float* image_rgba32f, const float* target,
+                             uint32_t target_channels, uint32_t width, uint32_t height, float lambda,
+                             float grad_scale, float* loss_out, float* dL_dimage_rgba32f, void* hip_stream);
 
 /* Report of the stream-ordered splat (no stats): waits for hip_stream and the context's view streams,
  * then returns (and clears) the counts since the last query. frames / views[v]: frames left

@@ -6,6 +6,7 @@ include/ptgs/ptgs.h); this package is its Python binding plus the host-side scen
 from ._abi import (ACCUM_RUNNING_MEAN, ACCUM_SUM, FLAG_COUNT_TRAVERSAL, FLAG_GPU_BVH, FLAG_GPU_LBVH, FLAG_PT_WAVEFRONT, FLAG_SPLAT_PUBLISH, FLAG_TIME_STAGES, HITDATA_DTYPE, MATERIAL_DTYPE,
                    PUNCTUAL_LIGHT_DTYPE, RAY_SAMPLE_DTYPE, VERTEX_DTYPE, PtgsError, RayPush, Ubo, load_library)
 from . import autograd
+from .autograd import l1_dssim
 from .capture import load_gaussian_ply
 from .densify import DensifyStats, densify_and_prune
 from .renderer import Renderer, torus_push
@@ -15,5 +16,5 @@ __all__ = [
     "ACCUM_RUNNING_MEAN", "ACCUM_SUM", "FLAG_COUNT_TRAVERSAL", "FLAG_GPU_BVH", "FLAG_GPU_LBVH", "FLAG_PT_WAVEFRONT", "FLAG_SPLAT_PUBLISH", "FLAG_TIME_STAGES", "HITDATA_DTYPE", "MATERIAL_DTYPE",
     "PUNCTUAL_LIGHT_DTYPE", "RAY_SAMPLE_DTYPE", "VERTEX_DTYPE", "PtgsError", "RayPush", "Ubo", "load_library",
     "Renderer", "torus_push", "Camera", "CameraPose", "Scene", "SceneBuilder", "cornell_box_scene", "make_ubo",
-    "mat4_inverse", "load_gaussian_ply", "autograd", "DensifyStats", "densify_and_prune",
+    "mat4_inverse", "load_gaussian_ply", "autograd", "DensifyStats", "densify_and_prune", "l1_dssim",
 ]

@@ -257,6 +257,7 @@ SYMBOLS = {
                                          C.POINTER(DensifyCounts), _P]),
     "ptgs_gaussians_densify_apply": (_I, [_P, _U, _U, _P, _P, _P, _P, _P, _P, _P, C.POINTER(DensifyRows), _U, _P,
                                           _P]),
+    "ptgs_image_loss_l1_dssim": (_I, [_P, _P, _P, _U, _U, _U, C.c_float, C.c_float, _P, _P, _P]),
     "ptgs_trace_depth_rows": (_I, [_P, C.POINTER(Ubo), _U, _U, _U, _U, _P, _P]),
     "ptgs_knn3_mean_dist2": (_I, [_P, _P, _U, _P, _P]),
     "ptgs_gaussians_from_points": (_I, [_P, _P, _P, _U, _P, _P, _P, _P, _P, _P]),

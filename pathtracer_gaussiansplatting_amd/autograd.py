@@ -15,6 +15,12 @@ Its forward is activate_gaussians, sh_colors and splat_gaussians, its backward s
 sh_colors_backward and activate_gaussians_backward: nothing is evaluated in torch. The backward pass consumes
 the frame its forward left in the renderer's workspace, so no other splat call of that renderer may come
 between the two (the backward then raises PtgsError). torch is imported on first use.
+
+l1_dssim() is the training loss of such a frame (Renderer.l1_dssim_loss, one HIP call for the value and the
+gradient):
+
+    loss = autograd.l1_dssim(renderer, img, target)       # 0.8 * L1 + 0.2 * (1 - SSIM)
+    loss.backward()
 """
 from __future__ import annotations
 
@@ -22,6 +28,7 @@ from . import _abi
 
 _FN = None
 _FN_SH = None
+_FN_LOSS = None
 
 
 def _publishing(renderer):
@@ -133,3 +140,40 @@ def splat_sh(renderer, means, log_scales, rotations, opacity_logits, sh, ubo, W:
     return _function_sh().apply(renderer, ubo, int(W), int(H), tuple(float(b) for b in bg),
                                 None if active_degree is None else int(active_degree), cam, means2d_grad, means,
                                 log_scales, rotations, opacity_logits, sh)
+
+
+def _function_loss():
+    global _FN_LOSS
+    if _FN_LOSS is not None:
+        return _FN_LOSS
+    import torch
+
+    class _L1Dssim(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, renderer, target, lam, image):
+            img = image.detach().contiguous()
+            grad = torch.empty_like(img) if ctx.needs_input_grad[3] else None
+            terms, grad = renderer.l1_dssim_loss(img, target.detach().contiguous(), lam=lam, grad_out=grad)
+            ctx.grad = grad
+            return terms[0]
+
+        @staticmethod
+        def backward(ctx, dL_dloss):
+            grad, ctx.grad = ctx.grad, None  # (scaled in place: a second backward would scale it twice)
+            if grad is None:
+                raise _abi.PtgsError("l1_dssim: the gradient was already consumed by an earlier backward")
+            return None, None, None, grad.mul_(dL_dloss)
+
+    _FN_LOSS = _L1Dssim
+    return _FN_LOSS
+
+
+def l1_dssim(renderer, image, target, lam: float = 0.2):
+    """The 3DGS training loss (1 - lam) * mean|image - target| + lam * (1 - SSIM(image, target)) as a 0-dim
+    tensor, differentiable with respect to image (RGBA32F [H, W, 4], e.g. splat_sh's output; target
+    [H, W, 3 or 4]; float32 device tensors). The forward is the one call ptgs_image_loss_l1_dssim, which
+    leaves the value and the gradient; the backward multiplies that gradient in place by the incoming scalar
+    gradient, on the device (the scalar is never read on the host): the only torch arithmetic. A trainer
+    that wants no torch op at all calls Renderer.l1_dssim_loss(img, target, grad_out=g, grad_scale=...) and
+    then img.backward(g)."""
+    return _function_loss().apply(renderer, target, float(lam), image)

@@ -30,6 +30,7 @@
 #include "splat.h"
 #include "splat_backward.h"
 #include "splat_densify.h"
+#include "splat_loss.h"
 #include "splat_sh.h"
 #include "textures.h"
 
@@ -52,6 +53,7 @@ struct ptgs_ctx {
   unsigned long long* counters = nullptr;  // 8 x u64
   SplatWorkspace* splat = nullptr;
   DensifyWorkspace* densify = nullptr;  // the densification plan (ptgs_gaussians_densify_plan / _apply)
+  LossWorkspace* loss = nullptr;  // the partial maps and sums of ptgs_image_loss_l1_dssim
   // ptgs_splat_gaussians_views: views 1.. run on their own workspaces and non-blocking streams,
   // forked from / joined back into the caller's stream with events (view 0 uses `splat` on it)
   SplatWorkspace* view_ws[PTGS_MAX_VIEWS] = {};
@@ -397,6 +399,7 @@ int ptgs_create(int hip_device, ptgs_ctx** out) {
   if (hipMemset(c->counters, 0, 8 * sizeof(unsigned long long)) != hipSuccess) { delete c; return PTGS_EHIP; }
   c->splat = splat_workspace_create();
   c->densify = densify_workspace_create();
+  c->loss = loss_workspace_create();
   *out = c;
   return PTGS_OK;
 }
@@ -409,6 +412,7 @@ void ptgs_destroy(ptgs_ctx* c) {
   ptgs::wf_workspace_free(c->wf);
   ptgs::free_pt_sched(c->pt_sched);
   densify_workspace_destroy(c->densify);
+  loss_workspace_destroy(c->loss);
   // (c->splat is one of the ring's workspaces once PTGS_FLAG_SPLAT_OVERLAP has been used: ring slot 0 is
   // the context's first one, freed here; the others below)
   splat_workspace_destroy(c->ov_ring[0] ? c->ov_ring[0] : c->splat);
@@ -1224,6 +1228,33 @@ int ptgs_gaussians_densify_apply(ptgs_ctx* c, uint32_t n, uint32_t n_out, const 
                                      rows, n_rows, source_out, (hipStream_t)stream);
   if (e == hipErrorInvalidValue) return fail(c, PTGS_ERANGE, "ptgs_gaussians_densify_apply: more elements than one launch holds");
   if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_densify_apply: %s", hipGetErrorString(e));
+  return PTGS_OK;
+}
+
+int ptgs_image_loss_l1_dssim(ptgs_ctx* c, const float* image, const float* target, uint32_t target_channels,
+                             uint32_t w, uint32_t h, float lambda, float grad_scale, float* loss_out,
+                             float* dL_dimage, void* stream) {
+  if (!c) return PTGS_EINVAL;
+  if (!image || !target || !loss_out) return fail(c, PTGS_EINVAL, "null argument");
+  if (w == 0 || h == 0 || w > LOSS_MAX_SIDE || h > LOSS_MAX_SIDE)
+    return fail(c, PTGS_EINVAL, "image of %u x %u: each side is 1 .. %u", w, h, LOSS_MAX_SIDE);
+  if (target_channels != 3 && target_channels != 4)
+    return fail(c, PTGS_EINVAL, "target_channels %u: 3 or 4", target_channels);
+  if (!(lambda >= 0.0f && lambda <= 1.0f)) return fail(c, PTGS_EINVAL, "lambda must be in [0, 1]");
+  if (!std::isfinite(grad_scale)) return fail(c, PTGS_EINVAL, "grad_scale must be finite");
+  const size_t pixels = (size_t)w * h;
+  if (dL_dimage) {
+    const char *g = (const char*)dL_dimage, *a = (const char*)image, *b = (const char*)target;
+    const size_t gb = pixels * 4 * sizeof(float), bb = pixels * target_channels * sizeof(float);
+    if ((g < a + gb && a < g + gb) || (g < b + bb && b < g + gb))
+      return fail(c, PTGS_EINVAL, "dL_dimage overlaps image or target");
+    if (!is_device_ptr(dL_dimage)) return fail(c, PTGS_EINVAL, "dL_dimage is not a device pointer");
+  }
+  if (!is_device_ptr(loss_out)) return fail(c, PTGS_EINVAL, "loss_out is not a device pointer");
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipError_t e = image_loss_l1_dssim(c->loss, image, target, target_channels, w, h, lambda, grad_scale, loss_out,
+                                           dL_dimage, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_image_loss_l1_dssim: %s", hipGetErrorString(e));
   return PTGS_OK;
 }
 

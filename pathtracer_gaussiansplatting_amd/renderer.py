@@ -420,6 +420,34 @@ class Renderer:
         self._chk(rc, "ptgs_gaussians_activate_backward")
         return ds, do
 
+    # ---------------------------------------------------------------- training loss
+    def l1_dssim_loss(self, image, target, lam: float = 0.2, grad_out=None, grad_scale: float = 1.0, terms_out=None,
+                      stream=None):
+        """ptgs_image_loss_l1_dssim: the 3DGS training loss (1 - lam) * mean|image - target| + lam * (1 - SSIM)
+        of a rendered RGBA32F frame image [H, W, 4] against target [H, W, 3 or 4] (contiguous float32 device
+        tensors, values in roughly [0, 1]; channels 0..2 take part). Returns (terms, grad): terms is a float32
+        device tensor [4] = (loss, l1, ssim, 0) (terms_out, or a new one) that is never read back here; grad is
+        grad_out, a float32 [H, W, 4] device tensor that receives grad_scale * dloss/dimage (alpha 0, every
+        element overwritten), or None when grad_out is None: only the terms are computed. Stream-ordered, no
+        host wait; reproducible from run to run (no atomics). A training loop that wants no torch arithmetic
+        calls this and then img.backward(grad)."""
+        import torch
+        if image.dim() != 3 or int(image.shape[2]) != 4:
+            raise _abi.PtgsError(f"image must be [H, W, 4] (got {tuple(image.shape)})")
+        h, w = int(image.shape[0]), int(image.shape[1])
+        c = int(target.shape[2]) if target.dim() == 3 else 0
+        if c not in (3, 4) or tuple(target.shape[:2]) != (h, w):
+            raise _abi.PtgsError(f"target must be [{h}, {w}, 3 or 4] (got {tuple(target.shape)})")
+        if terms_out is None:
+            terms_out = torch.empty(4, dtype=torch.float32, device=image.device)
+        self._f32(("image", image, h * w * 4), ("target", target, h * w * c), ("terms_out", terms_out, 4),
+                  *([("grad_out", grad_out, h * w * 4)] if grad_out is not None else []))
+        rc = self.lib.ptgs_image_loss_l1_dssim(self._h, _ptr(image), _ptr(target), c, w, h, float(lam),
+                                               float(grad_scale), _ptr(terms_out), _ptr(grad_out) or None,
+                                               _stream(stream))
+        self._chk(rc, "ptgs_image_loss_l1_dssim")
+        return terms_out, grad_out
+
     # ---------------------------------------------------------------- densification and pruning
     def densify_accumulate(self, means2d_grad, width: int, height: int, accum, denom, max_radii, radii=None,
                            stream=None):
