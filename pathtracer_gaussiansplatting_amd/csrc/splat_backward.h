@@ -17,7 +17,7 @@ struct SplatFrame {
   uint32_t n, W, H, tiles;
   const uint32_t* sorted_values;  // the tiles' depth-sorted Gaussians
   const uint2* ranges;            // per tile: [begin, end) in sorted_values
-  const float4* rec;              // three float4 per Gaussian (gs_preprocess_one)
+  const float4* rec;              // three float4 per Gaussian (gs_preprocess_one, splat_preprocess.h)
   const int* radii;               // 0: culled
 };
 void splat_last_frame(const SplatWorkspace* w, SplatFrame* out);

@@ -22,6 +22,7 @@
 
 #include <type_traits>
 
+#include "dev_buf.h"
 #include "splat_densify_math.h"
 
 namespace ptgs {
@@ -259,43 +260,26 @@ __global__ __launch_bounds__(DN_APPLY_WG) void gs_densify_apply_kernel(const DnA
     if (first + j * DN_APPLY_WG < count) dst[first + j * DN_APPLY_WG] = v[j];
 }
 
+// room for `need` elements of T, a quarter more when the buffer has to grow
 template <typename T>
-hipError_t dn_grow(T** p, size_t* cap, size_t need) {
-  if (need <= *cap) return hipSuccess;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = need + need / 4;
-  const hipError_t e = hipMalloc((void**)p, want * sizeof(T));
-  if (e == hipSuccess) *cap = want;
-  return e;
+hipError_t dn_ensure(DevBuf& b, size_t need) {
+  return b.ensure(need * sizeof(T), need / 4 * sizeof(T));
 }
 
 }  // namespace
 
 struct DensifyWorkspace {
-  uint8_t* fate = nullptr;
-  size_t fate_cap = 0;
-  uint32_t* block_sums = nullptr;  // [blocks][DN_FATES]: counts, then exclusive offsets
-  size_t sums_cap = 0;
-  uint32_t* totals = nullptr;  // DN_FATES words
-  size_t totals_cap = 0;
-  uint32_t* source = nullptr;
-  size_t source_cap = 0;
+  DevBuf fate;        // uint8_t per source Gaussian
+  DevBuf block_sums;  // uint32_t [blocks][DN_FATES]: counts, then exclusive offsets
+  DevBuf totals;      // DN_FATES words
+  DevBuf source;      // uint32_t per output Gaussian
   bool valid = false;  // the latest plan
   uint32_t n = 0, n_out = 0;
 };
 
 DensifyWorkspace* densify_workspace_create() { return new DensifyWorkspace(); }
 
-void densify_workspace_destroy(DensifyWorkspace* ws) {
-  if (!ws) return;
-  if (ws->fate) (void)hipFree(ws->fate);
-  if (ws->block_sums) (void)hipFree(ws->block_sums);
-  if (ws->totals) (void)hipFree(ws->totals);
-  if (ws->source) (void)hipFree(ws->source);
-  delete ws;
-}
+void densify_workspace_destroy(DensifyWorkspace* ws) { delete ws; }
 
 hipError_t densify_accumulate(const float* g2d, const int32_t* radii, uint32_t n, uint32_t W, uint32_t H, float* accum,
                               float* denom, float* max_radii, hipStream_t s) {
@@ -323,22 +307,23 @@ hipError_t densify_plan(DensifyWorkspace* ws, const float* scales, const float* 
   if (n == 0 || n > DN_MAX_N) return hipErrorInvalidValue;
   const uint32_t nb = (n + DN_BLOCK - 1) / DN_BLOCK;
   hipError_t e;
-  if ((e = dn_grow(&ws->fate, &ws->fate_cap, (size_t)n)) != hipSuccess) return e;
-  if ((e = dn_grow(&ws->block_sums, &ws->sums_cap, (size_t)nb * DN_FATES)) != hipSuccess) return e;
-  if ((e = dn_grow(&ws->totals, &ws->totals_cap, (size_t)DN_FATES)) != hipSuccess) return e;
-  gs_densify_decide_kernel<<<nb, DN_WG, 0, s>>>(scales, opacities, accum, denom, max_radii, n, p, ws->fate,
-                                                ws->block_sums);
+  if ((e = dn_ensure<uint8_t>(ws->fate, (size_t)n)) != hipSuccess) return e;
+  if ((e = dn_ensure<uint32_t>(ws->block_sums, (size_t)nb * DN_FATES)) != hipSuccess) return e;
+  if ((e = dn_ensure<uint32_t>(ws->totals, (size_t)DN_FATES)) != hipSuccess) return e;
+  gs_densify_decide_kernel<<<nb, DN_WG, 0, s>>>(scales, opacities, accum, denom, max_radii, n, p,
+                                                ws->fate.as<uint8_t>(), ws->block_sums.as<uint32_t>());
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  gs_densify_scan_kernel<<<1, DN_WG, 0, s>>>(ws->block_sums, nb, ws->totals);
+  gs_densify_scan_kernel<<<1, DN_WG, 0, s>>>(ws->block_sums.as<uint32_t>(), nb, ws->totals.as<uint32_t>());
   if ((e = hipGetLastError()) != hipSuccess) return e;
   uint32_t h[DN_FATES] = {};
-  if ((e = hipMemcpyAsync(h, ws->totals, sizeof(h), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(h, ws->totals.p, sizeof(h), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
   if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
   const uint64_t total = (uint64_t)h[0] + h[1] + 2ull * h[2];  // (<= 2 n <= 2^31)
   if (total > 0xFFFFFFFFull) return hipErrorInvalidValue;
   if (total) {
-    if ((e = dn_grow(&ws->source, &ws->source_cap, (size_t)total)) != hipSuccess) return e;
-    gs_densify_scatter_kernel<<<nb, DN_WG, 0, s>>>(ws->fate, n, ws->block_sums, ws->totals, ws->source);
+    if ((e = dn_ensure<uint32_t>(ws->source, (size_t)total)) != hipSuccess) return e;
+    gs_densify_scatter_kernel<<<nb, DN_WG, 0, s>>>(ws->fate.as<uint8_t>(), n, ws->block_sums.as<uint32_t>(),
+                                                   ws->totals.as<uint32_t>(), ws->source.as<uint32_t>());
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   out->survivors = h[0];
@@ -361,7 +346,7 @@ hipError_t densify_apply(const DensifyWorkspace* ws, const float* means, const f
   DnApply a{};
   a.n = ws->n;
   a.n_out = ws->n_out;
-  a.source = ws->source;
+  a.source = ws->source.as<uint32_t>();
   a.means = means;
   a.rotations = rotations;
   a.scales = scales;
@@ -394,7 +379,7 @@ hipError_t densify_apply(const DensifyWorkspace* ws, const float* means, const f
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (source_out)
-    e = hipMemcpyAsync(source_out, ws->source, (size_t)ws->n_out * sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
+    e = hipMemcpyAsync(source_out, ws->source.p, (size_t)ws->n_out * sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
   return e;
 }
 

@@ -25,6 +25,7 @@
 // second (halo re-reads come from the caches).
 #include "splat_loss.h"
 
+#include "dev_buf.h"
 #include "splat_loss_math.h"
 
 namespace ptgs {
@@ -300,36 +301,18 @@ __global__ __launch_bounds__(LS_WG) void gs_loss_final_kernel(const double* __re
 }
 static_assert(LS_STEP == LS_WG, "the final sum's step is its workgroup");
 
-template <typename T>
-hipError_t ls_grow(T** p, size_t* cap, size_t need) {
-  if (need <= *cap) return hipSuccess;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const hipError_t e = hipMalloc((void**)p, need * sizeof(T));
-  if (e == hipSuccess) *cap = need;
-  return e;
-}
-
 bool ls_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace
 
 struct LossWorkspace {
-  float* maps = nullptr;  // LS_MAPS planes of W x H
-  size_t maps_cap = 0;
-  double* partials = nullptr;  // (sum |a - b|, sum m) per workgroup
-  size_t partials_cap = 0;
+  DevBuf maps;      // float: LS_MAPS planes of W x H
+  DevBuf partials;  // double: (sum |a - b|, sum m) per workgroup
 };
 
 LossWorkspace* loss_workspace_create() { return new LossWorkspace(); }
 
-void loss_workspace_destroy(LossWorkspace* ws) {
-  if (!ws) return;
-  if (ws->maps) (void)hipFree(ws->maps);
-  if (ws->partials) (void)hipFree(ws->partials);
-  delete ws;
-}
+void loss_workspace_destroy(LossWorkspace* ws) { delete ws; }
 
 hipError_t image_loss_l1_dssim(LossWorkspace* ws, const float* image, const float* target, uint32_t channels,
                                uint32_t W, uint32_t H, float lambda, float grad_scale, float* loss_out, float* grad,
@@ -340,19 +323,22 @@ hipError_t image_loss_l1_dssim(LossWorkspace* ws, const float* image, const floa
   const uint32_t nwg = grid.x * grid.y;  // (<= 512 * 512)
   const size_t pixels = (size_t)W * H;
   hipError_t e;
-  if ((e = ls_grow(&ws->partials, &ws->partials_cap, 2 * (size_t)nwg)) != hipSuccess) return e;
-  if (grad && (e = ls_grow(&ws->maps, &ws->maps_cap, LS_MAPS * pixels)) != hipSuccess) return e;
+  // (grown to the exact size: no slack)
+  if ((e = ws->partials.ensure(2 * (size_t)nwg * sizeof(double), 0)) != hipSuccess) return e;
+  if (grad && (e = ws->maps.ensure(LS_MAPS * pixels * sizeof(float), 0)) != hipSuccess) return e;
+  float* const maps = ws->maps.as<float>();
+  double* const partials = ws->partials.as<double>();
   const bool vi = ls_aligned16(image), vt = ls_aligned16(target);
   if (grad) {
     if (channels == 4)
-      gs_loss_stats_kernel<4, true><<<grid, LS_WG, 0, s>>>(image, target, W, H, vi, vt, ws->maps, ws->partials);
+      gs_loss_stats_kernel<4, true><<<grid, LS_WG, 0, s>>>(image, target, W, H, vi, vt, maps, partials);
     else
-      gs_loss_stats_kernel<3, true><<<grid, LS_WG, 0, s>>>(image, target, W, H, vi, vt, ws->maps, ws->partials);
+      gs_loss_stats_kernel<3, true><<<grid, LS_WG, 0, s>>>(image, target, W, H, vi, vt, maps, partials);
   } else {
     if (channels == 4)
-      gs_loss_stats_kernel<4, false><<<grid, LS_WG, 0, s>>>(image, target, W, H, vi, vt, nullptr, ws->partials);
+      gs_loss_stats_kernel<4, false><<<grid, LS_WG, 0, s>>>(image, target, W, H, vi, vt, nullptr, partials);
     else
-      gs_loss_stats_kernel<3, false><<<grid, LS_WG, 0, s>>>(image, target, W, H, vi, vt, nullptr, ws->partials);
+      gs_loss_stats_kernel<3, false><<<grid, LS_WG, 0, s>>>(image, target, W, H, vi, vt, nullptr, partials);
   }
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const double n = 3.0 * (double)pixels;
@@ -360,14 +346,14 @@ hipError_t image_loss_l1_dssim(LossWorkspace* ws, const float* image, const floa
     const float k1 = (float)((double)grad_scale * (1.0 - (double)lambda) / n);
     const float k2 = (float)((double)grad_scale * (double)lambda / n);
     if (channels == 4)
-      gs_loss_grad_kernel<4><<<grid, LS_WG, 0, s>>>(image, target, W, H, vi, vt, ls_aligned16(grad), ws->maps, k1, k2,
+      gs_loss_grad_kernel<4><<<grid, LS_WG, 0, s>>>(image, target, W, H, vi, vt, ls_aligned16(grad), maps, k1, k2,
                                                     grad);
     else
-      gs_loss_grad_kernel<3><<<grid, LS_WG, 0, s>>>(image, target, W, H, vi, vt, ls_aligned16(grad), ws->maps, k1, k2,
+      gs_loss_grad_kernel<3><<<grid, LS_WG, 0, s>>>(image, target, W, H, vi, vt, ls_aligned16(grad), maps, k1, k2,
                                                     grad);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  gs_loss_final_kernel<<<1, LS_WG, 0, s>>>(ws->partials, nwg, 1.0 / n, lambda, loss_out);
+  gs_loss_final_kernel<<<1, LS_WG, 0, s>>>(partials, nwg, 1.0 / n, lambda, loss_out);
   return hipGetLastError();
 }
 

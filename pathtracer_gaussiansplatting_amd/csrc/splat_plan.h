@@ -1,6 +1,6 @@
 // splat_plan.h — the host's planning rules of the 3DGS forward pass (splat.hip): plain values in, plain
 // values out. No HIP include: tests/native/splat_plan_check.cpp builds it with a host compiler alone. The
-// racy mailbox hints a rule depends on (splat.hip, GsHostWord) are arguments, read by the caller at the
+// racy mailbox hints a rule depends on (splat_words.h, GsHostWord) are arguments, read by the caller at the
 // point of the frame call where the rule applies.
 #pragma once
 

@@ -1,4 +1,5 @@
-// splat_probe.h — measurement hooks of splat.hip, compiled out of the shipped library.
+// splat_probe.h — measurement hooks of the forward pass (splat.hip and its stage headers), compiled out of the
+// shipped library.
 //
 // Stamps (GS_STAMP builds, tools/gs_stamps.py): per-workgroup s_memrealtime (100 MHz) stamps at phase
 // boundaries of the fused front end (kind 0) and the blend (kind 1), read back with ptgs_debug_stamps.

@@ -41,7 +41,7 @@
 namespace ptgs {
 namespace {
 
-constexpr int SH_WG = 256;  // Gaussians per workgroup (the chunk granule of splat.hip)
+constexpr int SH_WG = 256;  // Gaussians per workgroup (the forward pass's chunk granule, splat_plan.h)
 constexpr int SH_BATCH = 4;  // staging loads in flight per work-item
 
 // Stage the block's nfl floats (rows of R, contiguous at src) into LDS rows of stride S with lane-contiguous

@@ -1,5 +1,5 @@
 """The integer outputs of the frames the headline times. Stream-ordered frames bin
-each Gaussian only to the tiles its alpha >= 1/255 box overlaps (splat.hip gs_preprocess_one, the
+each Gaussian only to the tiles its alpha >= 1/255 box overlaps (splat_preprocess.h gs_preprocess_one, the
 SplatCam::tight branch), not its whole 3-sigma rectangle; the oracle restates that binning
 (oracle_splat_gaussians_tight). PTGS_FLAG_SPLAT_PUBLISH_TIGHT makes a published frame bin the same way,
 through the same front ends, so the timed path's sorted keys / values / tile ranges (and radii / tiles

@@ -1,4 +1,4 @@
-"""The histogram windows of the fused splat front end (splat.hip gs_bin_fused_kernel, the `kw` loop).
+"""The histogram windows of the fused splat front end (splat_fused.h gs_bin_fused_kernel, the `kw` loop).
 An overlapped frame (PTGS_FLAG_SPLAT_OVERLAP) runs the 256-work-item workgroup shape, whose LDS histogram
 holds WINDOW = 2048 tiles: a 256-Gaussian chunk whose bounding tile rect within a band holds more tiles
 walks its slice once per window, and each walk counts, reserves and scatters only that window's pairs.
@@ -19,7 +19,7 @@ import scenes_util as U
 from pathtracer_gaussiansplatting_amd import Camera, make_ubo
 from pathtracer_gaussiansplatting_amd import synthetic as Y
 
-WINDOW = 2048  # GsFusedShape<256>::lds_cap (splat.hip; a static_assert there names this file)
+WINDOW = 2048  # GsFusedShape<256>::lds_cap (splat_plan.h; a static_assert there names this file)
 SLICE = 2048  # GsFusedShape<256>::slice: pairs per walked slice of a chunk
 CHUNK = 256  # GS_FUSED_THREADS: Gaussians per fused workgroup
 BAND_TILES = 8192  # GS_BAND_TILES
