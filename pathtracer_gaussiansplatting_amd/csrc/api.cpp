@@ -6,6 +6,12 @@
 //   recordCommandBuffer's vkCmdTraceRaysKHR :1971-1976 + rt_output_image running mean
 //       -> ptgs_trace_camera
 //   torus trace :1893-1900 / :2787-2794 -> ptgs_trace_torus
+//
+// Map: struct ptgs_ctx; the helpers every entry point shares (fail, HIPCHK, hip_rc, the argument checks);
+// the scene upload's builders and stages; context, communicator, trace and memory entry points; then the
+// rasterizers: the splat frame calls (splat_check_args, splat_render, splat_overlap_resources / _begin,
+// splat_finish over the context's SplatFrames: splat_frames.h owns, splat_run.h decides), the Gaussian
+// preparation, backward, densify and loss entry points, the splat's status / reserve / accessors, points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,16 +36,15 @@
 #include "splat.h"
 #include "splat_backward.h"
 #include "splat_densify.h"
+#include "splat_frames.h"
 #include "splat_loss.h"
 #include "splat_sh.h"
 #include "textures.h"
 
 using namespace ptgs;
 
-// frames in flight of PTGS_FLAG_SPLAT_OVERLAP: workspaces in the ring (the front end of call k may run
-// beside the blends of calls k - 1 .. k - depth + 1; PTGS_GS_OV_DEPTH=2 .. 4, default 3)
-#define PTGS_OV_RING 4        // workspaces the ring may hold (PTGS_GS_OV_DEPTH)
-#define PTGS_OV_DEPTH_DEFAULT 3
+static_assert(kSplatReportIncomplete == SPLAT_REPORT_INCOMPLETE && kSplatReportBadIds == SPLAT_REPORT_BAD_IDS,
+              "splat_run.h names the bits of SplatReport");
 
 struct ptgs_ctx {
   int device = 0;
@@ -51,30 +56,9 @@ struct ptgs_ctx {
   ptgs_scene_info info{};
   ptgs_scene_build build{};  // which builder's tree is resident (ptgs_scene_get_build)
   unsigned long long* counters = nullptr;  // 8 x u64
-  SplatWorkspace* splat = nullptr;
+  SplatFrames frames;  // the splat frame calls' workspaces, streams, events, run and pending reports
   DensifyWorkspace* densify = nullptr;  // the densification plan (ptgs_gaussians_densify_plan / _apply)
   LossWorkspace* loss = nullptr;  // the partial maps and sums of ptgs_image_loss_l1_dssim
-  // ptgs_splat_gaussians_views: views 1.. run on their own workspaces and non-blocking streams,
-  // forked from / joined back into the caller's stream with events (view 0 uses `splat` on it)
-  SplatWorkspace* view_ws[PTGS_MAX_VIEWS] = {};
-  hipStream_t view_stream[PTGS_MAX_VIEWS] = {};
-  hipEvent_t view_fork = nullptr, view_join[PTGS_MAX_VIEWS] = {};
-  // PTGS_FLAG_SPLAT_OVERLAP: a ring of workspaces (`splat` is always the latest call's; ov_ring[0] is the
-  // context's own first workspace), the front-end stream, the caller's stream at the start of a run of
-  // overlapped calls (ov_call[0]; see splat_overlap_begin), the front end's end
-  SplatWorkspace* ov_ring[PTGS_OV_RING] = {};
-  hipStream_t ov_stream = nullptr;
-  hipEvent_t ov_call[1] = {}, ov_done = nullptr;
-  uint32_t ov_pos = 0;      // ring slot of the latest overlapped call
-  uint32_t ov_depth = 0;    // workspaces in use (2 .. PTGS_OV_RING)
-  uint32_t pending_report = 0;  // earlier frames' reports a failing splat call collected (returned by the next)
-  uint32_t ov_started = 0;  // consecutive overlapped calls so far (0: the next one starts a run from the caller's stream)
-  // blend ordinals (SplatSeq): the device word the blends store theirs in, the next one, and per call of the
-  // run (k % 4) the ordinal of its blend (0: none launched) and its stream
-  unsigned long long* ov_flag = nullptr;
-  unsigned long long ov_next = 1;
-  unsigned long long ov_ord[4] = {};
-  hipStream_t ov_strm[4] = {};
   ptgs::WfWorkspace wf;  // wavefront path tracer buffers (PTGS_FLAG_PT_WAVEFRONT)
   ptgs::PtSched pt_sched;  // megakernel tile schedule (heavy tiles first)
   void* comm = nullptr;  // RCCL communicator (ptgs_comm_create)
@@ -98,6 +82,24 @@ int fail(ptgs_ctx* c, int code, const char* fmt, ...) {
     hipError_t e_ = (expr);                                                                 \
     if (e_ != hipSuccess) return fail(ctx, PTGS_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
+
+int hip_rc(ptgs_ctx* c, hipError_t e, const char* what) {
+  if (e != hipSuccess) return fail(c, PTGS_EHIP, "%s: %s", what, hipGetErrorString(e));
+  return PTGS_OK;
+}
+
+int check_image_size(ptgs_ctx* c, uint32_t w, uint32_t h) {
+  if (w == 0 || h == 0 || w > 32768 || h > 32768) return fail(c, PTGS_EINVAL, "bad image size %ux%u", w, h);
+  return PTGS_OK;
+}
+
+// row_ranges: [begin, end) per rank of the communicator, inside the image
+int check_row_ranges(ptgs_ctx* c, const uint32_t* row_ranges, uint32_t height) {
+  for (int g = 0; g < c->comm_ranks; ++g)
+    if (row_ranges[2 * g] > row_ranges[2 * g + 1] || row_ranges[2 * g + 1] > height)
+      return fail(c, PTGS_EINVAL, "bad row range of rank %d", g);
+  return PTGS_OK;
+}
 
 void free_scene(ptgs_ctx* c) {
   for (void* p : c->scene_allocs) (void)hipFree(p);
@@ -397,7 +399,6 @@ int ptgs_create(int hip_device, ptgs_ctx** out) {
   if (hipSetDevice(hip_device) != hipSuccess) { delete c; return PTGS_EHIP; }
   if (hipMalloc(&c->counters, 8 * sizeof(unsigned long long)) != hipSuccess) { delete c; return PTGS_EHIP; }
   if (hipMemset(c->counters, 0, 8 * sizeof(unsigned long long)) != hipSuccess) { delete c; return PTGS_EHIP; }
-  c->splat = splat_workspace_create();
   c->densify = densify_workspace_create();
   c->loss = loss_workspace_create();
   *out = c;
@@ -413,24 +414,8 @@ void ptgs_destroy(ptgs_ctx* c) {
   ptgs::free_pt_sched(c->pt_sched);
   densify_workspace_destroy(c->densify);
   loss_workspace_destroy(c->loss);
-  // (c->splat is one of the ring's workspaces once PTGS_FLAG_SPLAT_OVERLAP has been used: ring slot 0 is
-  // the context's first one, freed here; the others below)
-  splat_workspace_destroy(c->ov_ring[0] ? c->ov_ring[0] : c->splat);
-  for (int v = 0; v < PTGS_MAX_VIEWS; ++v) {
-    if (c->view_ws[v]) splat_workspace_destroy(c->view_ws[v]);
-    if (c->view_stream[v]) (void)hipStreamDestroy(c->view_stream[v]);
-    if (c->view_join[v]) (void)hipEventDestroy(c->view_join[v]);
-  }
-  if (c->view_fork) (void)hipEventDestroy(c->view_fork);
-  for (SplatWorkspace* w : c->ov_ring)  // (ring slot 0 is the context's first workspace: freed above)
-    if (w && w != c->ov_ring[0]) splat_workspace_destroy(w);
-  if (c->ov_stream) (void)hipStreamDestroy(c->ov_stream);
-  for (hipEvent_t ev : c->ov_call)
-    if (ev) (void)hipEventDestroy(ev);
-  if (c->ov_done) (void)hipEventDestroy(c->ov_done);
-  if (c->ov_flag) (void)hipFree(c->ov_flag);
   if (c->comm) (void)comm_destroy(c->comm);
-  delete c;
+  delete c;  // (~SplatFrames: the splat workspaces, streams, events and signal word)
 }
 
 int ptgs_comm_unique_id(uint8_t id[PTGS_COMM_ID_BYTES]) {
@@ -490,9 +475,7 @@ int ptgs_gather_rows(ptgs_ctx* c, float* image, uint32_t width, uint32_t height,
   if (!c->comm) return fail(c, PTGS_EINVAL, "no communicator (ptgs_comm_create)");
   if (root < 0 || root >= c->comm_ranks) return fail(c, PTGS_EINVAL, "bad root %d", root);
   if (!is_device_ptr(image)) return fail(c, PTGS_EINVAL, "image is not a device pointer");
-  for (int g = 0; g < c->comm_ranks; ++g)
-    if (row_ranges[2 * g] > row_ranges[2 * g + 1] || row_ranges[2 * g + 1] > height)
-      return fail(c, PTGS_EINVAL, "bad row range of rank %d", g);
+  if (const int bad = check_row_ranges(c, row_ranges, height)) return bad;
   HIPCHK(c, hipSetDevice(c->device));
   int e = comm_gather_rows(c->comm, image, (size_t)width * 4u, row_ranges, c->comm_ranks, c->comm_rank, root,
                            (hipStream_t)stream);
@@ -505,9 +488,7 @@ int ptgs_reduce_scatter_rows(ptgs_ctx* c, float* image, uint32_t width, uint32_t
   if (!c || !image || !row_ranges) return PTGS_EINVAL;
   if (!c->comm) return fail(c, PTGS_EINVAL, "no communicator (ptgs_comm_create)");
   if (!is_device_ptr(image)) return fail(c, PTGS_EINVAL, "image is not a device pointer");
-  for (int g = 0; g < c->comm_ranks; ++g)
-    if (row_ranges[2 * g] > row_ranges[2 * g + 1] || row_ranges[2 * g + 1] > height)
-      return fail(c, PTGS_EINVAL, "bad row range of rank %d", g);
+  if (const int bad = check_row_ranges(c, row_ranges, height)) return bad;
   HIPCHK(c, hipSetDevice(c->device));
   int e = comm_reduce_rows(c->comm, image, (size_t)width * 4u, row_ranges, c->comm_ranks, (hipStream_t)stream);
   if (e) return fail(c, PTGS_EHIP, "ncclReduce: %s", comm_error(e));
@@ -581,7 +562,7 @@ int ptgs_trace_camera_rows(ptgs_ctx* c, const ptgs_ubo* ubo, uint32_t w, uint32_
                            uint32_t accum_mode, void* stream) {
   if (!c || !ubo || !accum) return fail(c, PTGS_EINVAL, "null argument");
   if (!c->has_scene) return fail(c, PTGS_ENOSCENE, "no scene uploaded");
-  if (w == 0 || h == 0 || w > 32768 || h > 32768) return fail(c, PTGS_EINVAL, "bad image size %ux%u", w, h);
+  if (const int bad = check_image_size(c, w, h)) return bad;
   if (row_end > h) row_end = h;
   if (row_begin > row_end) return fail(c, PTGS_EINVAL, "bad row range");
   if (frame_stride == 0) return fail(c, PTGS_EINVAL, "frame_stride must be >= 1");
@@ -596,13 +577,11 @@ int ptgs_trace_camera_rows(ptgs_ctx* c, const ptgs_ubo* ubo, uint32_t w, uint32_
   if (c->flags & PTGS_FLAG_PT_WAVEFRONT) {
     e = ptgs::launch_pt_wavefront(c->wf, c->dsc, cp, accum, w, h, row_begin, row_end, spp, ubo->frame_count,
                                   frame_stride, accum_mode, c->counters, stats, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(c, PTGS_EHIP, "wavefront path tracer: %s", hipGetErrorString(e));
-    return PTGS_OK;
+    return hip_rc(c, e, "wavefront path tracer");
   }
   e = launch_pt_camera(c->dsc, cp, accum, w, h, row_begin, row_end, spp, ubo->frame_count, frame_stride, accum_mode,
                        c->counters, stats, &c->pt_sched, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "pt_camera launch: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "pt_camera launch");
 }
 
 int ptgs_trace_camera(ptgs_ctx* c, const ptgs_ubo* ubo, uint32_t w, uint32_t h, float* accum, uint32_t spp,
@@ -618,7 +597,7 @@ int ptgs_trace_depth_rows(ptgs_ctx* c, const ptgs_ubo* ubo, uint32_t w, uint32_t
                           uint32_t row_end, float* depth, void* stream) {
   if (!c || !ubo || !depth) return fail(c, PTGS_EINVAL, "null argument");
   if (!c->has_scene) return fail(c, PTGS_ENOSCENE, "no scene uploaded");
-  if (w == 0 || h == 0 || w > 32768 || h > 32768) return fail(c, PTGS_EINVAL, "bad image size %ux%u", w, h);
+  if (const int bad = check_image_size(c, w, h)) return bad;
   if (!is_device_ptr(depth)) return fail(c, PTGS_EINVAL, "depth is not a device pointer");
   HIPCHK(c, hipSetDevice(c->device));
   CamParams cp;
@@ -627,8 +606,7 @@ int ptgs_trace_depth_rows(ptgs_ctx* c, const ptgs_ubo* ubo, uint32_t w, uint32_t
   ViewMat vm;
   std::memcpy(vm.m, ubo->view, sizeof(vm.m));
   hipError_t e = launch_pt_depth(c->dsc, cp, vm, depth, w, h, row_begin, row_end, ubo->frame_count, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "pt_depth launch: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "pt_depth launch");
 }
 
 int ptgs_trace_torus(ptgs_ctx* c, const ptgs_ubo* ubo, const ptgs_ray_push* push, const ptgs_ray_sample* samples,
@@ -651,8 +629,7 @@ int ptgs_trace_torus(ptgs_ctx* c, const ptgs_ubo* ubo, const ptgs_ray_push* push
   while ((uint64_t)side * side < n) side++;
   hipError_t e = launch_pt_torus(c->dsc, cp, tp, samples, n, side, ubo->frame_count, hits, c->counters,
                                  (c->flags & PTGS_FLAG_COUNT_TRAVERSAL) != 0, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "pt_torus launch: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "pt_torus launch");
 }
 
 int ptgs_set_flags(ptgs_ctx* c, uint32_t flags) {
@@ -725,11 +702,11 @@ int ptgs_synchronize(ptgs_ctx* c) {
 extern "C" {
 
 // The argument checks of a splat frame that need no device work. Every entry point runs them before it
-// changes any state of the context (the overlap ring above all: a rejected call must leave `splat`, the
-// ring position and the run's blend ordinals as the latest rendered frame left them).
+// changes any state of the context (the overlap ring above all: a rejected call must leave the current
+// workspace, the ring position and the run's blend ordinals as the latest rendered frame left them).
 static int splat_check_args(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t w, uint32_t h,
                             const float* depth, const float* under, const float* out) {
-  if (w == 0 || h == 0 || w > 32768 || h > 32768) return fail(c, PTGS_EINVAL, "bad image size %ux%u", w, h);
+  if (const int bad = check_image_size(c, w, h)) return bad;
   if (g->count && (!is_device_ptr(g->means) || !is_device_ptr(g->scales) || !is_device_ptr(g->rotations) ||
                    !is_device_ptr(g->opacities) || !is_device_ptr(g->colors) || (g->ids && !is_device_ptr(g->ids))))
     return fail(c, PTGS_EINVAL, "gaussian arrays must be device pointers");
@@ -740,12 +717,12 @@ static int splat_check_args(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo
   return PTGS_OK;
 }
 
-// Renders one frame whose arguments passed splat_check_args; PTGS_OK means it was enqueued completely.
-// *report (SplatReport: an earlier frame was left incomplete / met ids >= count) is about
-// EARLIER frames of the workspace: the caller turns it into PTGS_EINCOMPLETE / PTGS_EBADIDS (splat_report)
+// Renders one frame whose arguments passed splat_check_args into workspace ws; PTGS_OK means it was enqueued
+// completely. *report (SplatReport: an earlier frame was left incomplete / met ids >= count) is about
+// EARLIER frames of the workspace: the caller turns it into PTGS_EINCOMPLETE / PTGS_EBADIDS (splat_finish)
 // once everything it renders is enqueued.
-static int splat_render(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t w, uint32_t h,
-                        const float bg[3], const float* depth, const float* under, uint32_t tile_row_begin,
+static int splat_render(ptgs_ctx* c, SplatWorkspace* ws, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t w,
+                        uint32_t h, const float bg[3], const float* depth, const float* under, uint32_t tile_row_begin,
                         uint32_t tile_row_end, float* out, ptgs_splat_stats* stats, void* stream, uint32_t* report,
                         const SplatOverlap* ov = nullptr, SplatSeq* seq = nullptr) {
   *report = 0;
@@ -773,66 +750,47 @@ static int splat_render(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ub
   a.stream = (hipStream_t)stream;
   a.ov = ov;
   a.seq = seq;
-  hipError_t e = splat_gaussians(c->splat, a, report);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "splat_gaussians: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  hipError_t e = splat_gaussians(ws, a, report);
+  return hip_rc(c, e, "splat_gaussians");
 }
 
-// (the frames of this call are rendered; the codes report earlier frames of the workspace(s))
-static int splat_report(ptgs_ctx* c, uint32_t report);
-// The reports a call collected (earlier frames' flags, consumed from the workspaces) and its own result.
-// Each kind of report is returned once, never dropped, one per call: a failing call keeps them all for
-// the next call; a successful one returns one of them (with any kept earlier: bad ids first)
-// and keeps the other for the call after it (splat_report; the order is ptgs.h's, PTGS_EBADIDS).
+// The reports a call collected (earlier frames' flags, consumed from the workspaces) and its own result rc:
+// which code the call returns and what is kept for the next call is latch_report's (splat_run.h).
+// (the frames of this call are rendered; the two report codes are about earlier frames of the workspace(s))
 static int splat_finish(ptgs_ctx* c, int rc, uint32_t report) {
-  report |= c->pending_report;
-  c->pending_report = 0;
-  if (rc != PTGS_OK) {
-    c->pending_report = report;
-    return rc;
+  const SplatLatch l = latch_report(c->frames.pending_report, rc == PTGS_OK, report);
+  c->frames.pending_report = l.pending;
+  switch (l.code) {
+    case SplatCode::BadIds:
+      return fail(c, PTGS_EBADIDS, "an earlier splat frame met ptgs_gaussians.ids entries >= count");
+    case SplatCode::Incomplete:
+      return fail(c, PTGS_EINCOMPLETE, "an earlier splat frame left tiles incomplete (spill pool exhausted; grown)");
+    default:
+      return rc;  // (SplatCode::Ok: rc is PTGS_OK; SplatCode::Own: the call's own code)
   }
-  return splat_report(c, report);
-}
-static int splat_report(ptgs_ctx* c, uint32_t report) {
-  if (report & SPLAT_REPORT_BAD_IDS) {
-    c->pending_report = report & SPLAT_REPORT_INCOMPLETE;  // (an incomplete frame too: the next call's PTGS_EINCOMPLETE)
-    return fail(c, PTGS_EBADIDS, "an earlier splat frame met ptgs_gaussians.ids entries >= count");
-  }
-  if (report & SPLAT_REPORT_INCOMPLETE)
-    return fail(c, PTGS_EINCOMPLETE, "an earlier splat frame left tiles incomplete (spill pool exhausted; grown)");
-  return PTGS_OK;
 }
 
 // PTGS_FLAG_SPLAT_OVERLAP: the call takes the ring's next workspace (the one of the call depth calls back)
 // and, for a stream-ordered frame, its front end runs on the context's second stream. The first call of a
 // run of overlapped calls starts it after everything the caller's stream holds; later calls' front ends
 // wait on the device for the earlier blends of their workspace only (gs_done_wait), so inputs the caller
-// writes during a run are not seen by it. A call without the flag ends the run (ov_started is cleared).
-// workspaces in the ring, fixed when a context first overlaps (PTGS_GS_OV_DEPTH=2 .. 4; A/B switch)
-static uint32_t overlap_depth() {
-  const char* v = getenv("PTGS_GS_OV_DEPTH");
-  const int x = v ? atoi(v) : PTGS_OV_DEPTH_DEFAULT;
-  return (uint32_t)std::max(2, std::min(x, PTGS_OV_RING));
-}
-
-static int splat_overlap_begin(ptgs_ctx* c, hipStream_t s, SplatOverlap* ov, SplatSeq* seq) {
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!c->ov_ring[0]) {  // the ring starts at the current workspace
-    c->ov_ring[0] = c->splat;
-    c->ov_pos = 0;
-    c->ov_depth = overlap_depth();
-  }
-  const uint32_t depth = c->ov_depth;
-  for (uint32_t i = 1; i < depth; ++i)
-    if (!c->ov_ring[i]) c->ov_ring[i] = splat_workspace_create();
-  if (!c->ov_stream) {
+// writes during a run are not seen by it. A call without the flag ends the run (end_run).
+//
+// What an overlapped call needs, created when a context first overlaps: the ring's other workspaces (their
+// number is fixed then: PTGS_GS_OV_DEPTH, A/B switch), the front-end stream, the two events, the signal word.
+static int splat_overlap_resources(ptgs_ctx* c) {
+  SplatFrames& f = c->frames;
+  if (!f.run.depth) f.run.depth = splat_ring_depth(getenv("PTGS_GS_OV_DEPTH"));
+  for (uint32_t i = 1; i < f.run.depth; ++i)
+    if (!f.ring[i]) f.ring[i] = splat_workspace_create();
+  if (!f.fe) {
     // the front end's queue at the highest priority, so its workgroups take the CU slots of the blend's
     // retiring workgroups early instead of waiting for the blend's tail (PTGS_GS_OV_PRIO=normal: A/B switch)
     int least = 0, greatest = 0, prio = 0;
     const char* pv = getenv("PTGS_GS_OV_PRIO");
     if (!(pv && !strcmp(pv, "normal")) && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess)
       prio = greatest;
-    HIPCHK(c, hipStreamCreateWithPriority(&c->ov_stream, hipStreamNonBlocking, prio));
+    HIPCHK(c, hipStreamCreateWithPriority(&f.fe, hipStreamNonBlocking, prio));
   }
   // (device-scope events: both streams are on this device, so no system-scope release (an L2 write-back)
   // is needed at the record; PTGS_GS_OV_FENCE=1 restores it: A/B switch)
@@ -840,42 +798,37 @@ static int splat_overlap_begin(ptgs_ctx* c, hipStream_t s, SplatOverlap* ov, Spl
     const char* v = getenv("PTGS_GS_OV_FENCE");
     return (unsigned)(hipEventDisableTiming | (v && !strcmp(v, "1") ? 0u : (unsigned)hipEventDisableSystemFence));
   }();
-  for (hipEvent_t* ev : {&c->ov_call[0], &c->ov_done})
+  for (hipEvent_t* ev : {&f.marker, &f.done})
     if (!*ev) HIPCHK(c, hipEventCreateWithFlags(ev, ev_flags));
-  if (!c->ov_flag) {  // (signal memory for the front end's wait-value packet; zero before any blend stores)
-    HIPCHK(c, hipExtMallocWithFlags((void**)&c->ov_flag, 8, hipMallocSignalMemory));
-    HIPCHK(c, hipMemset(c->ov_flag, 0, 8));
+  if (!f.signal) {  // (signal memory for the front end's wait-value packet; zero before any blend stores)
+    HIPCHK(c, hipExtMallocWithFlags((void**)&f.signal, 8, hipMallocSignalMemory));
+    HIPCHK(c, hipMemset(f.signal, 0, 8));
   }
+  return PTGS_OK;
+}
+
+static int splat_overlap_begin(ptgs_ctx* c, hipStream_t s, SplatOverlap* ov, SplatSeq* seq) {
+  HIPCHK(c, hipSetDevice(c->device));
+  if (const int rc = splat_overlap_resources(c)) return rc;
+  SplatFrames& f = c->frames;
   // the next ring slot; the workspace there was last used depth calls ago (call k - depth). Its blend ran
   // before the blend of call k - depth + 1 on the caller's stream, so once THAT blend has started (its
-  // ordinal in ov_flag, SplatSeq) the workspace is free: the front end's queue waits for that value and the
-  // caller's queue carries no marker (a marker beside the cross-queue barrier had cost it ~3-5 us per frame:
-  // tools/micro/queue_sync.hip, wait + marker 28.0 vs wait alone 25.1 us on a 22 us kernel; kernel trace
-  // 10.5 vs 6.0 us between two blends). The first call of a run waits for a marker of the caller's stream
-  // (everything enqueued before the run), as do calls whose ordering is not known (no blend launched, or a
-  // call on another stream: then a new marker).
-  const uint32_t cur = (c->ov_pos + 1) % depth;
-  c->ov_pos = cur;
-  c->splat = c->ov_ring[cur];
-  const uint32_t k = c->ov_started, back = depth - 1;
-  bool same = true;
-  for (uint32_t j = 1; j <= std::min(k, back); ++j) same = same && c->ov_strm[(k - j) & 3u] == s;
-  ov->fe = c->ov_stream;
-  ov->done = c->ov_done;
-  ov->wait = nullptr;
-  ov->wait_flag = nullptr;
-  ov->wait_ordinal = 0;
-  if (k >= back && same && c->ov_ord[(k - back) & 3u]) {
-    ov->wait_flag = c->ov_flag;
-    ov->wait_ordinal = c->ov_ord[(k - back) & 3u];
-  } else {
-    // (k < back on the run's stream: the workspace was last used before the run, so the marker recorded at
-    // the run's start (or a later one) covers it; otherwise a new marker)
-    if (!(k > 0 && k < back && same)) HIPCHK(c, hipEventRecord(c->ov_call[0], s));
-    ov->wait = c->ov_call[0];
-  }
-  seq->flag = c->ov_flag;
-  seq->ordinal = c->ov_next;
+  // ordinal in the signal word, SplatSeq) the workspace is free: the front end's queue waits for that value
+  // and the caller's queue carries no marker (a marker beside the cross-queue barrier had cost it ~3-5 us per
+  // frame: tools/micro/queue_sync.hip, wait + marker 28.0 vs wait alone 25.1 us on a 22 us kernel; kernel
+  // trace 10.5 vs 6.0 us between two blends). When that is not known the front end waits for a marker of the
+  // caller's stream instead (next_wait, splat_run.h, has the rule).
+  f.advance();
+  const SplatWait wait = next_wait(f.run, s);
+  if (wait.kind == SplatWait::NewMarker) HIPCHK(c, hipEventRecord(f.marker, s));
+  const bool by_ordinal = wait.kind == SplatWait::Ordinal;
+  ov->fe = f.fe;
+  ov->done = f.done;
+  ov->wait = by_ordinal ? nullptr : f.marker;
+  ov->wait_flag = by_ordinal ? f.signal : nullptr;
+  ov->wait_ordinal = wait.ordinal;
+  seq->flag = f.signal;
+  seq->ordinal = f.run.next_ordinal;
   seq->launched = false;
   // the blend's tile order: the front end's order workgroup from the workspace's previous frame (default),
   // or PTGS_GS_OV_ORDER=own: a launch behind the front end from the frame's own counts (A/B switch;
@@ -888,15 +841,6 @@ static int splat_overlap_begin(ptgs_ctx* c, hipStream_t s, SplatOverlap* ov, Spl
   return PTGS_OK;
 }
 
-// after the call's frame: its blend's ordinal and stream (see splat_overlap_begin)
-static void splat_overlap_end(ptgs_ctx* c, hipStream_t s, const SplatSeq& seq) {
-  const uint32_t k = c->ov_started;
-  c->ov_ord[k & 3u] = seq.launched ? seq.ordinal : 0u;
-  c->ov_strm[k & 3u] = s;
-  if (seq.launched) c->ov_next = seq.ordinal + 1u;
-  c->ov_started = k + 1u < 4u ? k + 1u : 4u + ((k + 1u) & 3u);  // (>= 4: every look-back valid; the index mod 4 kept)
-}
-
 static int splat_common(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t w, uint32_t h,
                         const float bg[3], const float* depth, const float* under, uint32_t tile_row_begin,
                         uint32_t tile_row_end, float* out, ptgs_splat_stats* stats, void* stream) {
@@ -905,21 +849,22 @@ static int splat_common(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ub
   SplatSeq seq{};
   const SplatOverlap* ovp = nullptr;
   // (before the ring advances: after a rejected call ptgs_splat_get_buffers / _get_tile_rows / _status_read
-  // still describe the latest rendered frame, and the run goes on as if the call had not been made: no
-  // entry of ov_ord / ov_strm is written and ov_started is not advanced, so the next front end's wait
-  // value is still the ordinal of a blend that splat_overlap_end recorded as launched, or the marker)
+  // still describe the latest rendered frame, and the run goes on as if the call had not been made: nothing
+  // is recorded in the run, so the next front end's wait value is still the ordinal of a blend that a call
+  // recorded as launched, or the marker)
   const int bad = splat_check_args(c, g, ubo, w, h, depth, under, out);
   if (bad != PTGS_OK) return bad;
+  SplatFrames& f = c->frames;
   if (c->flags & PTGS_FLAG_SPLAT_OVERLAP) {
     const int rc = splat_overlap_begin(c, (hipStream_t)stream, &ov, &seq);
     if (rc != PTGS_OK) return rc;
     ovp = &ov;  // (splat_gaussians runs a frame with stats / publish / stage timing serially anyway)
   } else {
-    c->ov_started = 0;
+    end_run(f.run);
   }
-  const int rc = splat_render(c, g, ubo, w, h, bg, depth, under, tile_row_begin, tile_row_end, out, stats, stream,
-                              &report, ovp, ovp ? &seq : nullptr);
-  if (ovp) splat_overlap_end(c, (hipStream_t)stream, seq);
+  const int rc = splat_render(c, f.current(), g, ubo, w, h, bg, depth, under, tile_row_begin, tile_row_end, out, stats,
+                              stream, &report, ovp, ovp ? &seq : nullptr);
+  if (ovp) record(f.run, stream, seq.launched, seq.ordinal);  // (its blend's ordinal and stream: next_wait)
   return splat_finish(c, rc, report);
 }
 
@@ -950,52 +895,53 @@ int ptgs_splat_gaussians_views(ptgs_ctx* c, const ptgs_gaussians* g, uint32_t n_
     if (bad != PTGS_OK) return bad;
   }
   HIPCHK(c, hipSetDevice(c->device));
-  c->ov_started = 0;  // (view 0 renders serially on the caller's stream with the latest workspace)
+  SplatFrames& f = c->frames;
+  end_run(f.run);  // (view 0 renders serially on the caller's stream with the latest workspace)
   const hipStream_t s = (hipStream_t)stream;
-  if (!c->view_fork) HIPCHK(c, hipEventCreateWithFlags(&c->view_fork, hipEventDisableTiming));
+  if (!f.fork) HIPCHK(c, hipEventCreateWithFlags(&f.fork, hipEventDisableTiming));
   // every view's pair buffer starts from the largest pair count any slot has seen (views of one
   // Gaussian set have similar counts): a fresh view workspace would otherwise start at 8 pairs per
   // Gaussian and skip its first over-capacity frame (reported by ptgs_splat_status_read)
-  uint32_t hint = splat_pair_hint(c->splat);
+  uint32_t hint = splat_pair_hint(f.current());
   for (uint32_t v = 1; v < n_views; ++v) {
-    if (!c->view_ws[v]) c->view_ws[v] = splat_workspace_create();
-    if (!c->view_stream[v]) HIPCHK(c, hipStreamCreateWithFlags(&c->view_stream[v], hipStreamNonBlocking));
-    if (!c->view_join[v]) HIPCHK(c, hipEventCreateWithFlags(&c->view_join[v], hipEventDisableTiming));
-    hint = std::max(hint, splat_pair_hint(c->view_ws[v]));
+    SplatFrames::View& vw = f.view(v);
+    if (!vw.ws) vw.ws = splat_workspace_create();
+    if (!vw.stream) HIPCHK(c, hipStreamCreateWithFlags(&vw.stream, hipStreamNonBlocking));
+    if (!vw.join) HIPCHK(c, hipEventCreateWithFlags(&vw.join, hipEventDisableTiming));
+    hint = std::max(hint, splat_pair_hint(vw.ws));
   }
   if (hint) {
     const uint32_t want = hint + hint / 8u;  // headroom for the views' differences
-    for (uint32_t v = 1; v < n_views; ++v) HIPCHK(c, splat_reserve(c->view_ws[v], want));
+    for (uint32_t v = 1; v < n_views; ++v) HIPCHK(c, splat_reserve(f.view(v).ws, want));
   }
-  HIPCHK(c, hipEventRecord(c->view_fork, s));  // the views start after the caller's earlier work
+  HIPCHK(c, hipEventRecord(f.fork, s));  // the views start after the caller's earlier work
   // on any failure after a view was forked, the views already launched are joined back into the
   // caller's stream before returning (later work there must not race them)
   uint32_t launched = 1;
   uint32_t report = 0;  // the views' reports about their earlier frames (PTGS_EINCOMPLETE / PTGS_EINVAL)
   auto join = [&]() {
-    for (uint32_t v = 1; v < launched; ++v) (void)hipStreamWaitEvent(s, c->view_join[v], 0);
+    for (uint32_t v = 1; v < launched; ++v) (void)hipStreamWaitEvent(s, f.view(v).join, 0);
   };
   for (uint32_t v = 1; v < n_views; ++v) {
-    hipError_t e = hipStreamWaitEvent(c->view_stream[v], c->view_fork, 0);
+    const SplatFrames::View& vw = f.view(v);
+    hipError_t e = hipStreamWaitEvent(vw.stream, f.fork, 0);
     if (e != hipSuccess) {
       join();
-      return splat_finish(c, fail(c, PTGS_EHIP, "hipStreamWaitEvent: %s", hipGetErrorString(e)), report);
+      return splat_finish(c, hip_rc(c, e, "hipStreamWaitEvent"), report);
     }
-    SplatWorkspace* keep = c->splat;
-    c->splat = c->view_ws[v];
     uint32_t rep = 0;
-    const int rc = splat_render(c, g, &ubos[v], w, h, bg, nullptr, nullptr, 0, ~0u, outs[v], nullptr, c->view_stream[v],
+    const int rc = splat_render(c, vw.ws, g, &ubos[v], w, h, bg, nullptr, nullptr, 0, ~0u, outs[v], nullptr, vw.stream,
                                 &rep);
-    c->splat = keep;
     report |= rep;  // (about earlier frames of view v's workspace: returned once every view is enqueued)
     // (record the join even after a failed view: kernels it did enqueue must be waited for)
-    e = hipEventRecord(c->view_join[v], c->view_stream[v]);
+    e = hipEventRecord(vw.join, vw.stream);
     if (e == hipSuccess) launched = v + 1;
     if (rc != PTGS_OK) { join(); return splat_finish(c, rc, report); }
-    if (e != hipSuccess) { join(); return splat_finish(c, fail(c, PTGS_EHIP, "hipEventRecord: %s", hipGetErrorString(e)), report); }
+    if (e != hipSuccess) { join(); return splat_finish(c, hip_rc(c, e, "hipEventRecord"), report); }
   }
   uint32_t rep = 0;
-  const int rc = splat_render(c, g, &ubos[0], w, h, bg, nullptr, nullptr, 0, ~0u, outs[0], nullptr, stream, &rep);
+  const int rc = splat_render(c, f.current(), g, &ubos[0], w, h, bg, nullptr, nullptr, 0, ~0u, outs[0], nullptr, stream,
+                              &rep);
   join();
   return splat_finish(c, rc, report | rep);
 }
@@ -1012,8 +958,7 @@ int ptgs_gaussians_sort_spatial(ptgs_ctx* c, const ptgs_gaussians* g, float* mea
   }
   HIPCHK(c, hipSetDevice(c->device));
   const hipError_t e = splat_sort_spatial(g, means, scales, rotations, opacities, colors, ids, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_sort_spatial: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "ptgs_gaussians_sort_spatial");
 }
 
 int ptgs_gaussians_chunk_bounds(ptgs_ctx* c, const ptgs_gaussians* g, float* bounds, void* stream) {
@@ -1022,8 +967,7 @@ int ptgs_gaussians_chunk_bounds(ptgs_ctx* c, const ptgs_gaussians* g, float* bou
     return fail(c, PTGS_EINVAL, "means / scales / bounds must be device pointers");
   HIPCHK(c, hipSetDevice(c->device));
   const hipError_t e = splat_chunk_bounds(g, bounds, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_chunk_bounds: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "ptgs_gaussians_chunk_bounds");
 }
 
 int ptgs_gaussians_sh_colors(ptgs_ctx* c, const float* means, const float* sh, uint32_t count, uint32_t sh_degree,
@@ -1039,8 +983,7 @@ int ptgs_gaussians_sh_colors(ptgs_ctx* c, const float* means, const float* sh, u
   HIPCHK(c, hipSetDevice(c->device));
   const hipError_t e =
       splat_sh_colors(means, sh, count, sh_degree, active_degree, camera_pos, colors, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_sh_colors: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "ptgs_gaussians_sh_colors");
 }
 
 int ptgs_gaussians_activate(ptgs_ctx* c, const float* log_scales, const float* opacity_logits, uint32_t count,
@@ -1053,8 +996,7 @@ int ptgs_gaussians_activate(ptgs_ctx* c, const float* log_scales, const float* o
     return fail(c, PTGS_EINVAL, "log_scales / opacity_logits / scales / opacities must be device pointers");
   HIPCHK(c, hipSetDevice(c->device));
   const hipError_t e = splat_sh_activate(log_scales, opacity_logits, count, scales, opacities, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_activate: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "ptgs_gaussians_activate");
 }
 
 int ptgs_gaussians_sh_colors_backward(ptgs_ctx* c, const float* means, const float* sh, uint32_t count,
@@ -1071,8 +1013,7 @@ int ptgs_gaussians_sh_colors_backward(ptgs_ctx* c, const float* means, const flo
   HIPCHK(c, hipSetDevice(c->device));
   const hipError_t e = splat_sh_colors_backward(means, sh, count, sh_degree, active_degree, camera_pos, dL_dcolors,
                                                 dL_dsh, dL_dmeans, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_sh_colors_backward: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "ptgs_gaussians_sh_colors_backward");
 }
 
 int ptgs_gaussians_activate_backward(ptgs_ctx* c, const float* scales, const float* opacities, uint32_t count,
@@ -1087,8 +1028,7 @@ int ptgs_gaussians_activate_backward(ptgs_ctx* c, const float* scales, const flo
   HIPCHK(c, hipSetDevice(c->device));
   const hipError_t e = splat_sh_activate_backward(scales, opacities, count, dL_dscales, dL_dopacities, dL_dlog_scales,
                                                   dL_dlogits, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_activate_backward: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "ptgs_gaussians_activate_backward");
 }
 
 int ptgs_gaussians_permute_sh(ptgs_ctx* c, const float* sh, uint32_t sh_degree, const uint32_t* ids, uint32_t count,
@@ -1102,8 +1042,7 @@ int ptgs_gaussians_permute_sh(ptgs_ctx* c, const float* sh, uint32_t sh_degree, 
     return fail(c, PTGS_EINVAL, "sh / ids / out must be device pointers");
   HIPCHK(c, hipSetDevice(c->device));
   const hipError_t e = splat_sh_permute(sh, sh_degree, ids, count, out, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_permute_sh: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "ptgs_gaussians_permute_sh");
 }
 
 int ptgs_splat_gaussians_backward(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t w, uint32_t h,
@@ -1121,7 +1060,7 @@ int ptgs_splat_gaussians_backward(ptgs_ctx* c, const ptgs_gaussians* g, const pt
     return fail(c, PTGS_EINVAL, "dL_dout / gradient arrays must be device pointers");
   if (ubo->proj[0] == 0.0f || ubo->proj[5] == 0.0f) return fail(c, PTGS_EINVAL, "degenerate projection");
   SplatFrame f;
-  splat_last_frame(c->splat, &f);
+  splat_last_frame(c->frames.current(), &f);
   if (!f.valid)
     return fail(c, PTGS_EINVAL,
                 "no frame to differentiate: the latest splat call must be a full-frame ptgs_splat_gaussians with "
@@ -1131,13 +1070,12 @@ int ptgs_splat_gaussians_backward(ptgs_ctx* c, const ptgs_gaussians* g, const pt
                 f.H, g->count, w, h);
   HIPCHK(c, hipSetDevice(c->device));
   float* acc = nullptr;
-  HIPCHK(c, splat_backward_scratch(c->splat, f.n, &acc));
+  HIPCHK(c, splat_backward_scratch(c->frames.current(), f.n, &acc));
   float mvp[16];
   mat4_mul(ubo->proj, ubo->view, mvp);
   const hipError_t e = splat_gaussians_backward(f, acc, g, ubo->view, mvp, ubo->proj[0], ubo->proj[5], bg, dL_dout, grads,
                                                 (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_splat_gaussians_backward: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "ptgs_splat_gaussians_backward");
 }
 
 int ptgs_densify_accumulate(ptgs_ctx* c, const float* g2d, const int32_t* radii, uint32_t n, uint32_t w, uint32_t h,
@@ -1149,8 +1087,7 @@ int ptgs_densify_accumulate(ptgs_ctx* c, const float* g2d, const int32_t* radii,
     return fail(c, PTGS_EINVAL, "accum / denom / max_radii must be device pointers");
   HIPCHK(c, hipSetDevice(c->device));
   const hipError_t e = densify_accumulate(g2d, radii, n, w, h, accum, denom, max_radii, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_densify_accumulate: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "ptgs_densify_accumulate");
 }
 
 int ptgs_gaussians_densify_plan(ptgs_ctx* c, const float* scales, const float* opacities, const float* accum,
@@ -1169,8 +1106,7 @@ int ptgs_gaussians_densify_plan(ptgs_ctx* c, const float* scales, const float* o
   HIPCHK(c, hipSetDevice(c->device));
   const hipError_t e = densify_plan(c->densify, scales, opacities, accum, denom, max_radii, n, *params, out,
                                     (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_densify_plan: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "ptgs_gaussians_densify_plan");
 }
 
 int ptgs_gaussians_densify_apply(ptgs_ctx* c, uint32_t n, uint32_t n_out, const float* means, const float* log_scales,
@@ -1227,8 +1163,7 @@ int ptgs_gaussians_densify_apply(ptgs_ctx* c, uint32_t n, uint32_t n_out, const 
   const hipError_t e = densify_apply(c->densify, means, log_scales, rotations, scales, noise, means_out, log_scales_out,
                                      rows, n_rows, source_out, (hipStream_t)stream);
   if (e == hipErrorInvalidValue) return fail(c, PTGS_ERANGE, "ptgs_gaussians_densify_apply: more elements than one launch holds");
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_gaussians_densify_apply: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "ptgs_gaussians_densify_apply");
 }
 
 int ptgs_image_loss_l1_dssim(ptgs_ctx* c, const float* image, const float* target, uint32_t target_channels,
@@ -1254,63 +1189,60 @@ int ptgs_image_loss_l1_dssim(ptgs_ctx* c, const float* image, const float* targe
   HIPCHK(c, hipSetDevice(c->device));
   const hipError_t e = image_loss_l1_dssim(c->loss, image, target, target_channels, w, h, lambda, grad_scale, loss_out,
                                            dL_dimage, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "ptgs_image_loss_l1_dssim: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "ptgs_image_loss_l1_dssim");
 }
 
 int ptgs_splat_status_read(ptgs_ctx* c, ptgs_splat_status* out, void* stream) {
   if (!c || !out) return PTGS_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));
-  for (int v = 1; v < PTGS_MAX_VIEWS; ++v)
-    if (c->view_stream[v]) HIPCHK(c, hipStreamSynchronize(c->view_stream[v]));
-  if (c->ov_stream) HIPCHK(c, hipStreamSynchronize(c->ov_stream));
+  SplatFrames& f = c->frames;
+  for (const SplatFrames::View& vw : f.views)
+    if (vw.stream) HIPCHK(c, hipStreamSynchronize(vw.stream));
+  if (f.fe) HIPCHK(c, hipStreamSynchronize(f.fe));
   *out = ptgs_splat_status{};
   out->pair_capacity = 0xFFFFFFFFu;
-  // (slot 0 also holds the other ring workspaces of PTGS_FLAG_SPLAT_OVERLAP: indices >= PTGS_MAX_VIEWS here)
-  for (int v = 0; v < PTGS_MAX_VIEWS + PTGS_OV_RING; ++v) {
-    SplatWorkspace* ws = v == 0 ? c->splat : v < PTGS_MAX_VIEWS ? c->view_ws[v] : c->ov_ring[v - PTGS_MAX_VIEWS];
-    if (!ws || (v >= PTGS_MAX_VIEWS && ws == c->splat)) continue;
-    const int slot = v >= PTGS_MAX_VIEWS ? 0 : v;
+  // (slot 0 is the whole ring: the current workspace, then the other ring workspaces of PTGS_FLAG_SPLAT_OVERLAP)
+  const hipError_t e = f.for_each_workspace([out](SplatRole role, uint32_t view, SplatWorkspace* ws) {
     SplatStatusOut so;
-    HIPCHK(c, splat_status(ws, true, &so));
-    out->views[slot] += so.incomplete;
+    if (const hipError_t e = splat_status(ws, true, &so)) return e;
+    out->views[view] += so.incomplete;
     out->frames += so.incomplete;
     out->spilled_tiles += so.spilled_tiles;
     out->incomplete_tiles += so.incomplete_tiles;
-    if (v < PTGS_MAX_VIEWS || so.last_pairs) out->pair_capacity = std::min(out->pair_capacity, so.capacity);
-    // the latest frame's pairs: the current workspace's (slot 0), else any view's
-    if (v < PTGS_MAX_VIEWS) out->last_pairs = std::max(out->last_pairs, so.last_pairs);
-    if (slot == 0) {
-      out->spill_capacity = v == 0 ? so.spill_capacity : std::min(out->spill_capacity, so.spill_capacity);
+    if (role != SplatRole::OtherRing || so.last_pairs) out->pair_capacity = std::min(out->pair_capacity, so.capacity);
+    // the latest frame's pairs: the current workspace's, else any view's
+    if (role != SplatRole::OtherRing) out->last_pairs = std::max(out->last_pairs, so.last_pairs);
+    if (role != SplatRole::View) {
+      out->spill_capacity =
+          role == SplatRole::Current ? so.spill_capacity : std::min(out->spill_capacity, so.spill_capacity);
       out->spill_demand = std::max(out->spill_demand, so.spill_demand);
     }
-  }
-  if (c->splat) splat_front_end_info(c->splat, &out->touched_runs, &out->fused);
+    return hipSuccess;
+  });
+  if (e != hipSuccess) return hip_rc(c, e, "splat_status(ws, true, &so)");
+  splat_front_end_info(f.current(), &out->touched_runs, &out->fused);
   return PTGS_OK;
 }
 
 int ptgs_splat_reserve(ptgs_ctx* c, uint32_t pairs) {
   if (!c) return PTGS_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, splat_reserve(c->splat, pairs));
-  for (int v = 1; v < PTGS_MAX_VIEWS; ++v)
-    if (c->view_ws[v]) HIPCHK(c, splat_reserve(c->view_ws[v], pairs));
-  for (SplatWorkspace* w : c->ov_ring)
-    if (w && w != c->splat) HIPCHK(c, splat_reserve(w, pairs));
-  return PTGS_OK;
+  const hipError_t e = c->frames.for_each_workspace(
+      [pairs](SplatRole, uint32_t, SplatWorkspace* ws) { return splat_reserve(ws, pairs); });
+  return hip_rc(c, e, "splat_reserve(ws, pairs)");
 }
 
 int ptgs_splat_get_buffers(const ptgs_ctx* c, ptgs_splat_buffers* out) {
   if (!c || !out) return PTGS_EINVAL;
-  splat_get_buffers(c->splat, out);
+  splat_get_buffers(c->frames.current(), out);
   return PTGS_OK;
 }
 
 int ptgs_splat_get_tile_rows(const ptgs_ctx* c, const uint64_t** rows, uint32_t* row_capacity) {
   if (!c || !rows || !row_capacity) return PTGS_EINVAL;
   const unsigned long long* r = nullptr;
-  splat_get_tile_rows(c->splat, &r, row_capacity);
+  splat_get_tile_rows(c->frames.current(), &r, row_capacity);
   *rows = (const uint64_t*)r;
   return PTGS_OK;
 }
@@ -1318,7 +1250,7 @@ int ptgs_splat_get_tile_rows(const ptgs_ctx* c, const uint64_t** rows, uint32_t*
 int ptgs_splat_stage_ms(ptgs_ctx* c, float out_ms[6]) {
   if (!c || !out_ms) return PTGS_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, splat_stage_ms(c->splat, out_ms));
+  HIPCHK(c, splat_stage_ms(c->frames.current(), out_ms));
   return PTGS_OK;
 }
 
@@ -1326,7 +1258,7 @@ int ptgs_splat_points(ptgs_ctx* c, const ptgs_ubo* ubo, const ptgs_ray_push* pus
                       const ptgs_ray_sample* samples, uint32_t n, uint32_t w, uint32_t h, uint32_t* rgba8,
                       float* depth, void* stream) {
   if (!c || !ubo || !push || !rgba8 || !depth) return fail(c, PTGS_EINVAL, "null argument");
-  if (w == 0 || h == 0 || w > 32768 || h > 32768) return fail(c, PTGS_EINVAL, "bad image size %ux%u", w, h);
+  if (const int bad = check_image_size(c, w, h)) return bad;
   if (n && (!is_device_ptr(hits) || (push->mode == 1 && !is_device_ptr(samples))))
     return fail(c, PTGS_EINVAL, "hits/samples must be device pointers");
   if (!is_device_ptr(rgba8) || !is_device_ptr(depth)) return fail(c, PTGS_EINVAL, "rgba8/depth must be device pointers");
@@ -1334,11 +1266,10 @@ int ptgs_splat_points(ptgs_ctx* c, const ptgs_ubo* ubo, const ptgs_ray_push* pus
   float mvp[16];
   mat4_mul(ubo->proj, ubo->view, mvp);
   unsigned long long* keys = nullptr;
-  HIPCHK(c, splat_point_keys(c->splat, (size_t)w * h, &keys));
+  HIPCHK(c, splat_point_keys(c->frames.current(), (size_t)w * h, &keys));
   hipError_t e = launch_splat_points(mvp, push->model, push->major_radius, push->minor_radius, push->height,
                                      push->mode, hits, samples, n, w, h, keys, depth, rgba8, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "splat_points: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "splat_points");
 }
 
 int ptgs_encode_srgb8(ptgs_ctx* c, const float* rgba32f, uint32_t w, uint32_t h, uint32_t* rgba8, void* stream) {
@@ -1346,8 +1277,7 @@ int ptgs_encode_srgb8(ptgs_ctx* c, const float* rgba32f, uint32_t w, uint32_t h,
   if (!is_device_ptr(rgba32f) || !is_device_ptr(rgba8)) return fail(c, PTGS_EINVAL, "buffers must be device pointers");
   HIPCHK(c, hipSetDevice(c->device));
   hipError_t e = launch_encode_srgb8(rgba32f, rgba8, w * h, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "encode_srgb8: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "encode_srgb8");
 }
 
 int ptgs_knn3_mean_dist2(ptgs_ctx* c, const float* xyz, uint32_t n, float* dist2, void* stream) {
@@ -1356,8 +1286,7 @@ int ptgs_knn3_mean_dist2(ptgs_ctx* c, const float* xyz, uint32_t n, float* dist2
   if (!is_device_ptr(xyz) || !is_device_ptr(dist2)) return fail(c, PTGS_EINVAL, "buffers must be device pointers");
   HIPCHK(c, hipSetDevice(c->device));
   hipError_t e = ptgs::knn3_mean_dist2(xyz, n, dist2, (hipStream_t)stream, nullptr);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "knn3_mean_dist2: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "knn3_mean_dist2");
 }
 
 int ptgs_gaussians_from_points(ptgs_ctx* c, const float* xyz, const uint8_t* rgb, uint32_t n, float* means,
@@ -1372,8 +1301,7 @@ int ptgs_gaussians_from_points(ptgs_ctx* c, const float* xyz, const uint8_t* rgb
   HIPCHK(c, hipSetDevice(c->device));
   hipError_t e = ptgs::gaussians_from_points(xyz, rgb, n, means, scales, rotations, opacities, colors,
                                              (hipStream_t)stream);
-  if (e != hipSuccess) return fail(c, PTGS_EHIP, "gaussians_from_points: %s", hipGetErrorString(e));
-  return PTGS_OK;
+  return hip_rc(c, e, "gaussians_from_points");
 }
 
 }  // extern "C"

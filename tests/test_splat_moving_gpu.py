@@ -663,3 +663,67 @@ def test_gaussians_overlap_rejected_call_keeps_latest_frame(native_lib, oracle_l
     finally:
         r.close()
         rb.close()
+
+
+def test_gaussians_every_workspace_is_reserved_read_and_freed(native_lib, monkeypatch):
+    """The three paths that visit every workspace of a context (the ring of PTGS_FLAG_SPLAT_OVERLAP at depth
+    4, the view workspaces 1..3): ptgs_splat_reserve grows them all (pair_capacity is the minimum over the
+    workspaces, so it reaches the reserved count only if each one was reserved), ptgs_splat_status_read sums
+    them all (frames == 0), and ptgs_destroy frees them all (a second context then renders a frame equal to
+    the serial one bit for bit)."""
+    from pathtracer_gaussiansplatting_amd import Renderer
+    monkeypatch.setenv("PTGS_GS_OV_DEPTH", "4")  # (read when a context first overlaps)
+    W, H, n = 64, 64, 2000
+    g = Y.gaussians_c2(n, seed=39)
+    ubos = [orbit_ubo(k, W, H) for k in range(8)]
+    dg = {k: _dev(v) for k, v in g.items()}
+    rb = Renderer(0)
+    try:
+        serial = [torch.zeros((H, W, 4), dtype=torch.float32, device="cuda") for _ in ubos]
+        for u, o in zip(ubos, serial):
+            rb.splat_gaussians(dg, u, W, H, o)
+        torch.cuda.synchronize()
+    finally:
+        rb.close()
+    outs = [torch.full((H, W, 4), -7.0, dtype=torch.float32, device="cuda") for _ in ubos]
+    views = [torch.full((H, W, 4), -7.0, dtype=torch.float32, device="cuda") for _ in range(4)]
+    r = Renderer(0)
+    try:
+        r.set_splat_overlap(True)
+        for k in range(6):  # every ring workspace has rendered
+            r.splat_gaussians(dg, ubos[k], W, H, outs[k])
+        r.splat_gaussians_views(dg, ubos[:4], W, H, views)
+        torch.cuda.synchronize()
+        st = r.splat_status()
+        assert st.last_pairs > 0 and st.frames == 0, (st.last_pairs, st.frames)
+        P = 4 * int(st.last_pairs)
+        r.splat_reserve(P)
+        r.splat_gaussians(dg, ubos[6], W, H, outs[6])
+        r.splat_gaussians_views(dg, ubos[4:8], W, H, views)
+        torch.cuda.synchronize()
+        st = r.splat_status()
+        assert st.pair_capacity >= P, (st.pair_capacity, P)
+        assert st.frames == 0, st.frames
+        # (8 pairs per Gaussian, a fresh workspace's buffer, is already above 4 x last_pairs at this size: a
+        # second reserve above every workspace's capacity is the one that fails if a workspace is left out)
+        P2 = 2 * int(st.pair_capacity) + 1
+        r.splat_reserve(P2)
+        r.splat_gaussians(dg, ubos[6], W, H, outs[6])
+        r.splat_gaussians_views(dg, ubos[4:8], W, H, views)
+        torch.cuda.synchronize()
+        st = r.splat_status()
+        assert st.pair_capacity >= P2, (st.pair_capacity, P2)
+        assert st.frames == 0, st.frames
+        diff = [k for k in range(7) if not torch.equal(outs[k], serial[k])]
+        diff += [4 + v for v in range(4) if not torch.equal(views[v], serial[4 + v])]
+        assert not diff, diff
+    finally:
+        r.close()
+    r2 = Renderer(0)
+    try:
+        out = torch.full((H, W, 4), -7.0, dtype=torch.float32, device="cuda")
+        r2.splat_gaussians(dg, ubos[7], W, H, out)
+        torch.cuda.synchronize()
+        assert torch.equal(out, serial[7])
+    finally:
+        r2.close()
