@@ -40,7 +40,9 @@ extern "C" {
                              * ptgs_gaussian_grads), ptgs_gaussians_sh_colors_backward,
                              * ptgs_gaussians_activate_backward, ptgs_densify_accumulate,
                              * ptgs_gaussians_densify_plan, ptgs_gaussians_densify_apply (with their three
-                             * structs), ptgs_image_loss_l1_dssim; ptgs_read_gaussian_ply in ptgs_host.h */
+                             * structs), ptgs_image_loss_l1_dssim, ptgs_gaussians_adam_step,
+                             * ptgs_gaussians_opacity_reset (with the structs ptgs_adam_rows and
+                             * ptgs_adam_params); ptgs_read_gaussian_ply in ptgs_host.h */
 
 /* ---------------- error codes ---------------- */
 #define PTGS_OK 0
@@ -821,6 +823,68 @@ int ptgs_gaussians_densify_apply(ptgs_ctx* ctx, uint32_t n, uint32_t n_out, cons
 int ptgs_image_loss_l1_dssim(ptgs_ctx* ctx, const float* image_rgba32f, const float* target,
                              uint32_t target_channels, uint32_t width, uint32_t height, float lambda,
                              float grad_scale, float* loss_out, float* dL_dimage_rgba32f, void* hip_stream);
+
+/* The optimizer step of a training run: Adam (Kingma & Ba; no weight decay, no amsgrad) over every per-Gaussian
+ * parameter array in one launch, optionally skipping the Gaussians the view did not see (the `sparse_adam` of
+ * Kerbl et al.'s trainer, after Taming-3DGS), and the trainer's opacity reset. All arrays are device pointers.
+ *
+ * ptgs_gaussians_adam_step: rows[0 .. n_rows) (1 <= n_rows <= 16, read by the host during the call) are the
+ * parameter arrays, each with its gradient and its two moments, n rows of `width` floats. Every operation is
+ * an IEEE f32 add / sub / mul / div / sqrt in the order written (no FMA, no transcendental on the device, no
+ * atomics), so a float32 restatement is reproduced bit for bit. The host computes once per call
+ *   ob1 = 1.0f - beta1;  ob2 = 1.0f - beta2                                   (f32)
+ *   bc1 = (float)(1.0 - pow((double)beta1, (double)step))
+ *   bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step))
+ *   per row: ss = lr / bc1;  ss_head = lr_head / bc1                         (f32 divisions)
+ * and every element, with g its gradient and c its column (its index within the row), becomes
+ *   m' = (beta1 * m) + (ob1 * g)
+ *   v' = (beta2 * v) + ((ob2 * g) * g)
+ *   d  = (sqrt(v') / bc2s) + eps
+ *   p' = p - ((c < head ? ss_head : ss) * (m' / d))
+ * head splits a row's rate: the first `head` floats step with lr_head (the SH DC term of a [16, 3] row: head 3),
+ * the others with lr. step counts the calls of the run, 1 for the first; it is global: a Gaussian that was
+ * skipped is corrected like one that was not, as in the trainer's sparse Adam.
+ * radii: NULL, or n int32 (the frame's ptgs_splat_buffers.radii). With radii, a Gaussian with radii[i] <= 0 is
+ * left untouched in param, exp_avg and exp_avg_sq of every row, bit for bit (and none of them is read); with
+ * NULL every Gaussian steps (a dense Adam). With PTGS_FLAG_SPLAT_OVERLAP the published radii may be rewritten
+ * by the next frame's front end: pass the frame's own radii only for frames that are not overlapped, or a copy.
+ * Bit-exactness holds for finite inputs whose intermediates are normal numbers or zero; with g == 0 and v == 0
+ * the update is exactly 0 (0 / eps). Subnormal intermediates give finite results, but are outside the bit-exact
+ * claim. NaN and Inf gradients propagate and are not handled. Any width >= 1 and any 4-byte-aligned base are
+ * accepted (16-byte accesses are used only where the width and all four bases of a row allow).
+ * Stream-ordered, allocates nothing, no host wait; two calls on the same inputs give the same bits.
+ * PTGS_EINVAL (message in ptgs_last_error, nothing enqueued): a null ctx, rows or params; n_rows == 0 or > 16;
+ * a null param / grad / exp_avg / exp_avg_sq; a width of 0; head > width; step == 0; beta1 or beta2 NaN or
+ * outside [0, 1); eps NaN, negative or infinite; an lr or lr_head that is not finite; a written array (param,
+ * exp_avg, exp_avg_sq) that overlaps another array of the table or radii; a written array that is not a device
+ * pointer. PTGS_ERANGE: more elements than one launch holds. n == 0: PTGS_OK before the rows' pointers are
+ * looked at, nothing is launched.
+ *
+ * ptgs_gaussians_opacity_reset (the trainer's reset_opacity, every 3000 iterations), in exact arithmetic:
+ *   cap = (float)log((double)max_opacity / (1.0 - (double)max_opacity))     (host)
+ *   logit' = logit > cap ? cap : logit                                       (a NaN stays)
+ * and zeros to every element of exp_avg and exp_avg_sq (n floats each) where they are given: the trainer
+ * replaces the opacity's moments by zeros for all Gaussians. The trainer computes inverse_sigmoid(min(sigmoid(x),
+ * 0.01)), which rounds a logit below the cap through a sigmoid and back; this form leaves such a logit as it is.
+ * Stream-ordered, allocates nothing. PTGS_EINVAL: a null ctx or opacity_logits; max_opacity NaN or not in
+ * (0, 1); the three arrays overlapping; one of them not a device pointer. n == 0: PTGS_OK, nothing launched. */
+typedef struct ptgs_adam_rows {      /* one per-Gaussian parameter array; 48 bytes */
+    float* param;                    /* n rows of `width` floats, updated in place */
+    const float* grad;               /* n rows, read only */
+    float* exp_avg;                  /* n rows, updated in place */
+    float* exp_avg_sq;               /* n rows, updated in place */
+    uint32_t width;                  /* floats per Gaussian, >= 1 */
+    uint32_t head;                   /* the first `head` floats of every row step with lr_head; 0: none; <= width */
+    float lr;
+    float lr_head;
+} ptgs_adam_rows;
+typedef struct ptgs_adam_params { float beta1, beta2, eps; uint32_t step; } ptgs_adam_params;  /* step: 1 for the first */
+#define PTGS_ADAM_MAX_ROWS 16
+int ptgs_gaussians_adam_step(ptgs_ctx* ctx, uint32_t n, const ptgs_adam_rows* rows, uint32_t n_rows,
+                             const ptgs_adam_params* params, const int32_t* radii /* NULL: every row */,
+                             void* hip_stream);
+int ptgs_gaussians_opacity_reset(ptgs_ctx* ctx, float* opacity_logits, uint32_t n, float max_opacity,
+                                 float* exp_avg /* NULL or n */, float* exp_avg_sq /* NULL or n */, void* hip_stream);
 
 /* Report of the stream-ordered splat (no stats): waits for hip_stream and the context's view streams,
  * then returns (and clears) the counts since the last query. frames / views[v]: frames left

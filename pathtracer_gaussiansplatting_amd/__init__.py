@@ -9,6 +9,7 @@ from . import autograd
 from .autograd import l1_dssim
 from .capture import load_gaussian_ply
 from .densify import DensifyStats, densify_and_prune
+from .optim import GaussianAdam, expon_lr
 from .renderer import Renderer, torus_push
 from .scene import Camera, CameraPose, Scene, SceneBuilder, cornell_box_scene, make_ubo, mat4_inverse
 
@@ -17,4 +18,5 @@ __all__ = [
     "PUNCTUAL_LIGHT_DTYPE", "RAY_SAMPLE_DTYPE", "VERTEX_DTYPE", "PtgsError", "RayPush", "Ubo", "load_library",
     "Renderer", "torus_push", "Camera", "CameraPose", "Scene", "SceneBuilder", "cornell_box_scene", "make_ubo",
     "mat4_inverse", "load_gaussian_ply", "autograd", "DensifyStats", "densify_and_prune", "l1_dssim",
+    "GaussianAdam", "expon_lr",
 ]

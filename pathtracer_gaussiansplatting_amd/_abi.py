@@ -172,6 +172,20 @@ class DensifyRows(C.Structure):
 DENSIFY_MAX_ROWS = 16
 
 
+class AdamRows(C.Structure):
+    """ptgs_adam_rows: one per-Gaussian parameter array of ptgs_gaussians_adam_step with its gradient and moments."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("width", C.c_uint32), ("head", C.c_uint32), ("lr", C.c_float), ("lr_head", C.c_float)]
+
+
+class AdamParams(C.Structure):
+    """ptgs_adam_params: step is 1 for the first call of a run."""
+    _fields_ = [("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("step", C.c_uint32)]
+
+
+ADAM_MAX_ROWS = 16
+
+
 class SplatStats(C.Structure):
     _fields_ = [("num_rendered", C.c_uint32), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32),
                 ("num_visible", C.c_uint32), ("fused", C.c_uint32)]
@@ -258,6 +272,8 @@ SYMBOLS = {
     "ptgs_gaussians_densify_apply": (_I, [_P, _U, _U, _P, _P, _P, _P, _P, _P, _P, C.POINTER(DensifyRows), _U, _P,
                                           _P]),
     "ptgs_image_loss_l1_dssim": (_I, [_P, _P, _P, _U, _U, _U, C.c_float, C.c_float, _P, _P, _P]),
+    "ptgs_gaussians_adam_step": (_I, [_P, _U, C.POINTER(AdamRows), _U, C.POINTER(AdamParams), _P, _P]),
+    "ptgs_gaussians_opacity_reset": (_I, [_P, _P, _U, C.c_float, _P, _P, _P]),
     "ptgs_trace_depth_rows": (_I, [_P, C.POINTER(Ubo), _U, _U, _U, _U, _P, _P]),
     "ptgs_knn3_mean_dist2": (_I, [_P, _P, _U, _P, _P]),
     "ptgs_gaussians_from_points": (_I, [_P, _P, _P, _U, _P, _P, _P, _P, _P, _P]),

@@ -34,6 +34,8 @@
 #include "scene_flatten.h"
 #include "comm.h"
 #include "splat.h"
+#include "splat_adam.h"
+#include "splat_adam_math.h"
 #include "splat_backward.h"
 #include "splat_densify.h"
 #include "splat_frames.h"
@@ -1078,6 +1080,20 @@ int ptgs_splat_gaussians_backward(ptgs_ctx* c, const ptgs_gaussians* g, const pt
   return hip_rc(c, e, "ptgs_splat_gaussians_backward");
 }
 
+// An array of a call as a byte range (densify apply, Adam step); out: the call writes it.
+struct Span {
+  const char* p;
+  size_t bytes;
+  bool out;
+};
+
+// does the written span i overlap another span? (two written spans are compared once, from the earlier one)
+static bool span_overlaps(const Span* sp, uint32_t ns, uint32_t i) {
+  for (uint32_t j = 0; j < ns; ++j)
+    if (j != i && (j > i || !sp[j].out) && sp[i].p < sp[j].p + sp[j].bytes && sp[j].p < sp[i].p + sp[i].bytes) return true;
+  return false;
+}
+
 int ptgs_densify_accumulate(ptgs_ctx* c, const float* g2d, const int32_t* radii, uint32_t n, uint32_t w, uint32_t h,
                             float* accum, float* denom, float* max_radii, void* stream) {
   if (!c) return PTGS_EINVAL;
@@ -1129,11 +1145,6 @@ int ptgs_gaussians_densify_apply(ptgs_ctx* c, uint32_t n, uint32_t n_out, const 
   if (!means || !log_scales || !rotations || !scales || !noise || !means_out || !log_scales_out)
     return fail(c, PTGS_EINVAL, "null argument");
   // every input and output as a byte range: an output may overlap nothing else
-  struct Span {
-    const char* p;
-    size_t bytes;
-    bool out;
-  };
   Span sp[7 + 2 * PTGS_DENSIFY_MAX_ROWS + 1];
   uint32_t ns = 0;
   auto span = [&](const void* p, size_t count, size_t width, bool out) {
@@ -1154,9 +1165,8 @@ int ptgs_gaussians_densify_apply(ptgs_ctx* c, uint32_t n, uint32_t n_out, const 
   if (source_out) span(source_out, n_out, 1, true);
   for (uint32_t i = 0; i < ns; ++i) {
     if (!sp[i].out) continue;
-    for (uint32_t j = 0; j < ns; ++j)
-      if (j != i && (j > i || !sp[j].out) && sp[i].p < sp[j].p + sp[j].bytes && sp[j].p < sp[i].p + sp[i].bytes)
-        return fail(c, PTGS_EINVAL, "an output aliases an input or another output (every dst differs from every src)");
+    if (span_overlaps(sp, ns, i))
+      return fail(c, PTGS_EINVAL, "an output aliases an input or another output (every dst differs from every src)");
     if (!is_device_ptr(sp[i].p)) return fail(c, PTGS_EINVAL, "an output is not a device pointer");
   }
   HIPCHK(c, hipSetDevice(c->device));
@@ -1190,6 +1200,70 @@ int ptgs_image_loss_l1_dssim(ptgs_ctx* c, const float* image, const float* targe
   const hipError_t e = image_loss_l1_dssim(c->loss, image, target, target_channels, w, h, lambda, grad_scale, loss_out,
                                            dL_dimage, (hipStream_t)stream);
   return hip_rc(c, e, "ptgs_image_loss_l1_dssim");
+}
+
+int ptgs_gaussians_adam_step(ptgs_ctx* c, uint32_t n, const ptgs_adam_rows* rows, uint32_t n_rows,
+                             const ptgs_adam_params* params, const int32_t* radii, void* stream) {
+  if (!c) return PTGS_EINVAL;
+  if (!rows || !params) return fail(c, PTGS_EINVAL, "null argument");
+  if (n_rows == 0 || n_rows > PTGS_ADAM_MAX_ROWS)
+    return fail(c, PTGS_EINVAL, "n_rows %u: 1 .. %d", n_rows, PTGS_ADAM_MAX_ROWS);
+  if (params->step == 0) return fail(c, PTGS_EINVAL, "step 0: the first step is 1");
+  if (!(params->beta1 >= 0.0f && params->beta1 < 1.0f) || !(params->beta2 >= 0.0f && params->beta2 < 1.0f))
+    return fail(c, PTGS_EINVAL, "beta1 and beta2 must be in [0, 1)");
+  if (!(params->eps >= 0.0f) || !std::isfinite(params->eps)) return fail(c, PTGS_EINVAL, "eps must be finite and >= 0");
+  for (uint32_t k = 0; k < n_rows; ++k) {
+    if (rows[k].width == 0) return fail(c, PTGS_EINVAL, "rows[%u] has width 0", k);
+    if (rows[k].head > rows[k].width)
+      return fail(c, PTGS_EINVAL, "rows[%u] has head %u above its width %u", k, rows[k].head, rows[k].width);
+    if (!std::isfinite(rows[k].lr) || !std::isfinite(rows[k].lr_head))
+      return fail(c, PTGS_EINVAL, "rows[%u] has an lr / lr_head that is not finite", k);
+  }
+  if (n == 0) return PTGS_OK;  // (empty arrays may be null)
+  // every array as a byte range: a written one may overlap nothing else
+  Span sp[4 * PTGS_ADAM_MAX_ROWS + 1];
+  uint32_t ns = 0;
+  for (uint32_t k = 0; k < n_rows; ++k) {
+    const ptgs_adam_rows& r = rows[k];
+    if (!r.param || !r.grad || !r.exp_avg || !r.exp_avg_sq)
+      return fail(c, PTGS_EINVAL, "rows[%u] has a null param / grad / exp_avg / exp_avg_sq", k);
+    const size_t bytes = (size_t)n * r.width * sizeof(float);
+    sp[ns++] = Span{(const char*)r.param, bytes, true};
+    sp[ns++] = Span{(const char*)r.grad, bytes, false};
+    sp[ns++] = Span{(const char*)r.exp_avg, bytes, true};
+    sp[ns++] = Span{(const char*)r.exp_avg_sq, bytes, true};
+  }
+  if (radii) sp[ns++] = Span{(const char*)radii, (size_t)n * sizeof(int32_t), false};
+  for (uint32_t i = 0; i < ns; ++i) {
+    if (!sp[i].out) continue;
+    if (span_overlaps(sp, ns, i))
+      return fail(c, PTGS_EINVAL, "a written array (param, exp_avg, exp_avg_sq) overlaps another array of the call");
+    if (!is_device_ptr(sp[i].p)) return fail(c, PTGS_EINVAL, "a written array is not a device pointer");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipError_t e = adam_step(n, rows, n_rows, *params, radii, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(c, PTGS_ERANGE, "ptgs_gaussians_adam_step: more elements than one launch holds");
+  return hip_rc(c, e, "ptgs_gaussians_adam_step");
+}
+
+int ptgs_gaussians_opacity_reset(ptgs_ctx* c, float* logits, uint32_t n, float max_opacity, float* exp_avg,
+                                 float* exp_avg_sq, void* stream) {
+  if (!c) return PTGS_EINVAL;
+  if (!(max_opacity > 0.0f && max_opacity < 1.0f)) return fail(c, PTGS_EINVAL, "max_opacity must be in (0, 1)");
+  if (n == 0) return PTGS_OK;  // (empty arrays may be null)
+  if (!logits) return fail(c, PTGS_EINVAL, "null argument");
+  const char* a[3] = {(const char*)logits, (const char*)exp_avg, (const char*)exp_avg_sq};
+  const size_t bytes = (size_t)n * sizeof(float);
+  for (int i = 0; i < 3; ++i) {
+    if (!a[i]) continue;
+    for (int j = i + 1; j < 3; ++j)
+      if (a[j] && a[i] < a[j] + bytes && a[j] < a[i] + bytes)
+        return fail(c, PTGS_EINVAL, "opacity_logits, exp_avg and exp_avg_sq overlap");
+    if (!is_device_ptr(a[i])) return fail(c, PTGS_EINVAL, "an output is not a device pointer");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipError_t e = opacity_reset(logits, n, adam_reset_cap(max_opacity), exp_avg, exp_avg_sq, (hipStream_t)stream);
+  return hip_rc(c, e, "ptgs_gaussians_opacity_reset");
 }
 
 int ptgs_splat_status_read(ptgs_ctx* c, ptgs_splat_status* out, void* stream) {

@@ -13,7 +13,8 @@ kernels of csrc/splat_densify.hip: nothing N-sized is evaluated in torch.
 params is the dict of the five leaf tensors of a checkpoint ("means", "log_scales", "rotations",
 "opacity_logits", "sh"); the call returns five new leaves. With a torch.optim.Adam its exp_avg / exp_avg_sq move
 with their rows (zeros for new Gaussians), `step` is kept and the param groups point at the new leaves, so the
-optimizer keeps running. torch is imported on first use.
+optimizer keeps running; an optim.GaussianAdam is treated alike (its ten moment arrays, its step_count, its
+leaves). torch is imported on first use.
 """
 from __future__ import annotations
 
@@ -82,7 +83,16 @@ def densify_and_prune(renderer, params: dict, stats: DensifyStats, *, grad_thres
     rows = [(d["rotations"], False), (d["opacity_logits"], False), (d["sh"], False)]
     moved = []  # (key, moment name) in the order of the rows after the three above
     states = {}
-    if optimizer is not None:
+    from .optim import GaussianAdam
+    ours = isinstance(optimizer, GaussianAdam)
+    if ours:
+        if any(optimizer.params[k] is not p[k] for k in PARAM_KEYS):
+            raise _abi.PtgsError("a parameter is not the GaussianAdam's own leaf")
+        for k in PARAM_KEYS:
+            for m in _MOMENTS:
+                rows.append((getattr(optimizer, m)[k].view(n, -1), True))
+                moved.append((k, m))
+    elif optimizer is not None:
         if not isinstance(optimizer, torch.optim.Adam) or any(g.get("amsgrad") for g in optimizer.param_groups):
             raise _abi.PtgsError("densify_and_prune moves the state of a torch.optim.Adam without amsgrad")
         for k in PARAM_KEYS:
@@ -97,7 +107,11 @@ def densify_and_prune(renderer, params: dict, stats: DensifyStats, *, grad_thres
                                                         scales, noise, rows, stream=stream)
     new = {"means": means_out, "log_scales": ls_out, "rotations": outs[0], "opacity_logits": outs[1], "sh": outs[2]}
     new = {k: v.requires_grad_(p[k].requires_grad) for k, v in new.items()}
-    if optimizer is not None:
+    if ours:  # step_count stays as it is
+        optimizer.params = dict(new)
+        for (k, m), t in zip(moved, outs[3:]):
+            getattr(optimizer, m)[k] = t.view(new[k].shape)
+    elif optimizer is not None:
         moments = {km: t for km, t in zip(moved, outs[3:])}
         for k in PARAM_KEYS:
             group, at, st = states[k]

@@ -524,6 +524,64 @@ class Renderer:
         self._chk(rc, "ptgs_gaussians_densify_apply")
         return means_out, ls_out, outs, source
 
+    # ---------------------------------------------------------------- optimizer step
+    def adam_step(self, rows, *, step: int, betas=(0.9, 0.999), eps: float = 1e-15, radii=None, masked: bool = False,
+                  stream=None):
+        """ptgs_gaussians_adam_step: one Adam step over every per-Gaussian array of rows in one launch. rows: a
+        sequence of (param, grad, exp_avg, exp_avg_sq, lr) or (..., lr, head, lr_head), float32 device tensors
+        [N, ...] of one shape per entry (at most 16 entries); the first `head` floats of each row step with
+        lr_head. param, exp_avg and exp_avg_sq are updated in place through their pointers (behind autograd's
+        back: pass detached leaves, after the backward). step: 1 for the first call of a run.
+        masked=True steps only the Gaussians the published frame saw (radius > 0; the latest splat of this
+        renderer, which must have N Gaussians, and not an overlapped frame) and leaves the others untouched;
+        radii (int32 [N]) are used instead of the frame's when given, and imply masked. masked=False without
+        radii is a dense Adam. Stream-ordered, no host wait; reproducible (no atomics)."""
+        import torch
+        rows = list(rows)
+        if not rows or len(rows) > _abi.ADAM_MAX_ROWS:
+            raise _abi.PtgsError(f"{len(rows)} rows: 1 .. {_abi.ADAM_MAX_ROWS}")
+        n = int(rows[0][0].shape[0])
+        arr = (_abi.AdamRows * len(rows))()
+        for k, r in enumerate(rows):
+            if len(r) not in (5, 7):
+                raise _abi.PtgsError(f"rows[{k}] must be (param, grad, exp_avg, exp_avg_sq, lr[, head, lr_head])")
+            p, g, m, v, lr = r[:5]
+            head, lr_head = (int(r[5]), float(r[6])) if len(r) == 7 else (0, 0.0)
+            if p.shape[0] != n or p.numel() == 0 and n:
+                raise _abi.PtgsError(f"rows[{k}] must have {n} non-empty rows (got {tuple(p.shape)})")
+            self._f32((f"rows[{k}].param", p, p.numel()), (f"rows[{k}].grad", g, p.numel()),
+                      (f"rows[{k}].exp_avg", m, p.numel()), (f"rows[{k}].exp_avg_sq", v, p.numel()))
+            arr[k].param, arr[k].grad, arr[k].exp_avg, arr[k].exp_avg_sq = _ptr(p), _ptr(g), _ptr(m), _ptr(v)
+            arr[k].width, arr[k].head = (p.numel() // n if n else 1), head
+            arr[k].lr, arr[k].lr_head = float(lr), lr_head
+        if radii is not None:
+            if radii.dtype != torch.int32 or radii.numel() != n:
+                raise _abi.PtgsError(f"radii must be int32 with {n} elements (got {radii.dtype}, {radii.numel()})")
+            rp = _ptr(radii) or None
+        elif masked:
+            b = self.splat_buffers()
+            if b.num_gaussians != n or (n and not b.radii):
+                raise _abi.PtgsError(f"the published frame has {b.num_gaussians} gaussians, the step {n}: "
+                                     "a masked adam_step follows a published splat of the same Gaussians")
+            rp = b.radii or None
+        else:
+            rp = None
+        prm = _abi.AdamParams(float(betas[0]), float(betas[1]), float(eps), int(step))
+        rc = self.lib.ptgs_gaussians_adam_step(self._h, n, arr, len(rows), C.byref(prm), rp, _stream(stream))
+        self._chk(rc, "ptgs_gaussians_adam_step")
+
+    def opacity_reset(self, opacity_logits, max_opacity: float = 0.01, exp_avg=None, exp_avg_sq=None, stream=None):
+        """ptgs_gaussians_opacity_reset: the trainer's reset_opacity in place: every logit above
+        logit(max_opacity) becomes that value, and the opacity's Adam moments (float32 [N] each, optional) are
+        zeroed for every Gaussian. Stream-ordered."""
+        n = int(opacity_logits.numel())
+        self._f32(("opacity_logits", opacity_logits, n),
+                  *([("exp_avg", exp_avg, n)] if exp_avg is not None else []),
+                  *([("exp_avg_sq", exp_avg_sq, n)] if exp_avg_sq is not None else []))
+        rc = self.lib.ptgs_gaussians_opacity_reset(self._h, _ptr(opacity_logits) or None, n, float(max_opacity),
+                                                   _ptr(exp_avg) or None, _ptr(exp_avg_sq) or None, _stream(stream))
+        self._chk(rc, "ptgs_gaussians_opacity_reset")
+
     def permute_sh(self, sh, ids, stream=None):
         """ptgs_gaussians_permute_sh: sh[ids] as a new tensor: the SH rows of the copy that
         sort_gaussians_spatial returned with these ids."""
