@@ -401,6 +401,23 @@ __device__ __forceinline__ void box4(const Ray& r, const DevScene& sc, int node,
 #ifndef PTGS_PT_NODE64_PIN
 #define PTGS_PT_NODE64_PIN 1
 #endif
+// PTGS_PT_PK_SLAB: the near and the far plane of one axis and child share the multiplier and the addend, so the
+// six slab distances of a child are three two-element FMAs {near, far} (v_pk_fma_f32: the shared operands are
+// broadcast by op_sel, no pairing moves), and the four tf * 1.0000004f are two two-element multiplies. Each
+// element is the same single-rounding operation as the scalar form: tn, tf, the hit masks and the image do not
+// change. An explicit builtin, not a contracted multiply-add and not the SLP vectoriser (build.py). Only
+// box4_q: the float-plane box4 above is not touched (pairing its children needed moves and measured -1.4%).
+// Off: closest-hit node step 217 -> 203 instructions (145 -> 131 VALU), shadow node step 164 -> 151 (108 -> 94),
+// 12 v_pk_fma_f32 + 2 v_pk_mul_f32 per step and no v_mov added, and C3 at 64 spp 6 346 -> 6 034 Mrays/s (-4.9%;
+// with the multiplies left scalar, PTGS_PT_PK_SLAB_MUL=0: 6 082, -4.2%; tools/ab_pt.py, images identical). A packed
+// f32 operation takes longer to issue here than the two scalar ones it replaces (profiles/r10_summary.md), which
+// is also why pt_kernels.hip is built without the SLP vectoriser (build.py).
+#ifndef PTGS_PT_PK_SLAB
+#define PTGS_PT_PK_SLAB 0
+#endif
+#ifndef PTGS_PT_PK_SLAB_MUL  // (with PK_SLAB) 0: the four multiplies stay scalar
+#define PTGS_PT_PK_SLAB_MUL 1
+#endif
 template <bool N64>
 __device__ __forceinline__ Ray node64_ray(const Ray& r) {
   Ray q = r;
@@ -430,6 +447,43 @@ __device__ __forceinline__ void box4_q(const Ray& r, const DevScene& sc, int nod
   const uint32_t nY = gy ? p.y : p.x, fY = gy ? p.x : p.y;
   const uint32_t nZ = gz ? p.w : p.z, fZ = gz ? p.z : p.w;
   const uint32_t CH[4] = {ch.x, ch.y, ch.z, ch.w};
+#if PTGS_PT_PK_SLAB
+  typedef float f2 __attribute__((ext_vector_type(2)));
+  const f2 SX = {sx, sx}, SY = {sy, sy}, SZ = {sz, sz}, CX = {cx, cx}, CY = {cy, cy}, CZ = {cz, cz};
+  float TN[4], TF[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const f2 qx = {node64_q(nX, j), node64_q(fX, j)}, qy = {node64_q(nY, j), node64_q(fY, j)};
+    const f2 qz = {node64_q(nZ, j), node64_q(fZ, j)};
+    const f2 x = __builtin_elementwise_fma(qx, SX, CX);  // {near, far}
+    const f2 y = __builtin_elementwise_fma(qy, SY, CY);
+    const f2 z = __builtin_elementwise_fma(qz, SZ, CZ);
+    TN[j] = fmaxf(fmaxf(x.x, y.x), fmaxf(z.x, r.tmin));
+#if PTGS_PT_ASM_MIN
+    float tf;
+    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(tf) : "v"(x.y), "v"(y.y), "v"(z.y));
+    asm("v_min_f32 %0, %1, %2" : "=v"(tf) : "v"(tf), "v"(tcap));
+    TF[j] = tf;
+#else
+    TF[j] = fminf(fminf(x.y, y.y), fminf(z.y, tcap));
+#endif
+  }
+#if PTGS_PT_PK_SLAB_MUL
+  const f2 K = {1.0000004f, 1.0000004f};
+  const f2 f01 = (f2){TF[0], TF[1]} * K, f23 = (f2){TF[2], TF[3]} * K;
+  const float TFK[4] = {f01.x, f01.y, f23.x, f23.y};
+#else
+  const float TFK[4] = {TF[0] * 1.0000004f, TF[1] * 1.0000004f, TF[2] * 1.0000004f, TF[3] * 1.0000004f};
+#endif
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    unsigned long long hm = __builtin_amdgcn_ballot_w64(TN[j] <= TFK[j]);
+    if (j >= 2) hm &= __builtin_amdgcn_ballot_w64(CH[j] != 0u);
+    o.tn[j] = __builtin_amdgcn_inverse_ballot_w64(hm) ? TN[j] : __builtin_huge_valf();
+    o.c[j] = (int)CH[j];
+    o.hm[j] = hm;
+  }
+#else
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const float x0 = __builtin_fmaf(node64_q(nX, j), sx, cx), x1 = __builtin_fmaf(node64_q(fX, j), sx, cx);
@@ -450,6 +504,7 @@ __device__ __forceinline__ void box4_q(const Ray& r, const DevScene& sc, int nod
     o.c[j] = (int)CH[j];
     o.hm[j] = hm;
   }
+#endif
 }
 template <bool N64>
 __device__ __forceinline__ void box4_sel(const Ray& r, const DevScene& sc, int node, float tcap, Box4& o) {
@@ -465,10 +520,10 @@ __device__ __forceinline__ void cswap4(Box4& b, int i, int j) {
 }
 // The next node of a closest-hit walk after a 4-wide node test: the nearest hit child, the other hit
 // children pushed farthest first; no hit child: pop().
-template <typename Push, typename Pop>
-__device__ __forceinline__ int enter_box4(Box4& b, Push push, Pop pop) {
+// (enter_box4_hit: the same for a lane with a hit child, for the walk that pops at a site of its own)
+template <typename Push>
+__device__ __forceinline__ int enter_box4_hit(Box4& b, Push push) {
   const unsigned long long h0 = b.hm[0], h1 = b.hm[1], h2 = b.hm[2], h3 = b.hm[3];
-  if (!__builtin_amdgcn_inverse_ballot_w64(h0 | h1 | h2 | h3)) return pop();
   cswap4(b, 0, 1); cswap4(b, 2, 3); cswap4(b, 0, 2); cswap4(b, 1, 3); cswap4(b, 1, 2);
   // (the sorted hits come first: at least 4 / 3 / 2 of the four children hit, as lane masks)
   const unsigned long long a01 = h0 & h1, o01 = h0 | h1, a23 = h2 & h3, o23 = h2 | h3;
@@ -477,6 +532,11 @@ __device__ __forceinline__ int enter_box4(Box4& b, Push push, Pop pop) {
   if (__builtin_amdgcn_inverse_ballot_w64((a01 & o23) | (o01 & a23))) push(b.c[2], b.tn[2]);
   if (__builtin_amdgcn_inverse_ballot_w64(a01 | a23 | (o01 & o23))) push(b.c[1], b.tn[1]);
   return b.c[0];
+}
+template <typename Push, typename Pop>
+__device__ __forceinline__ int enter_box4(Box4& b, Push push, Pop pop) {
+  if (!__builtin_amdgcn_inverse_ballot_w64(b.hm[0] | b.hm[1] | b.hm[2] | b.hm[3])) return pop();
+  return enter_box4_hit(b, push);
 }
 
 // SS: the LDS stack's stride (work-items sharing it); OVF: overflow entries beyond the LDS part (0 for
@@ -497,6 +557,37 @@ __device__ __forceinline__ int enter_box4(Box4& b, Push push, Pop pop) {
 // that tests the empty stack as a second loop exit instead of popping DONE as a never-culled word: 5 886.
 #ifndef PTGS_PT_STACK_CULL
 #define PTGS_PT_STACK_CULL 1
+#endif
+// PTGS_PT_ONE_POP: one pop site in the node step of trace_closest instead of two copies of the culling pop loop
+// (enter_box4's "no child hit" pop, and the pop after the entered leaf is parked). A lane needs a pop when no
+// child was hit, or when its nearest child is a leaf and it holds none.
+//   1: every lane visits the nodes and leaves it visited before, in the same order. A lane that pops a leaf
+//      while it holds none parks it and pops again: a second pass of the one pop loop (its condition: the word
+//      is culled, or it was parked), not a second site.
+//   2: the lane pops once. A leaf popped by a lane with no hit child leaves the node loop in `node`, where the
+//      code after the loop tests it as it tests a second leaf. The closest hit is a minimum over candidates, so
+//      the hits are the same; a lane no longer walks on past such a leaf, so the lane steps move.
+//   0: the two sites (shipped).
+// Both one-site forms are off. Closest-hit node step in the ISA 217 -> 193 (form 1) and 195 (form 2)
+// instructions, and C3 at 64 spp, interleaved with the SLP packing off (build.py): 6 529 Mrays/s with the two
+// sites, 6 508 with form 1, 6 529 with form 2; on top of PTGS_PT_ULOOP 6 548 -> 6 533 and 6 547. The second pop
+// site is an exec region of its own, entered only in a step in which a lane parks a leaf; how often a wave
+// skips it was not measured, and the time did not follow the static count. Form 2 visits C3's nodes in 296.5 M wave steps instead
+// of 288.1 M (lane steps -0.1%). C5's DEEP instantiation, whose pop carries the overflow's branches, gains from
+// form 2 (3 266 -> 3 339 Mrays/s), but no more than 0.5% beyond what PTGS_PT_ULOOP gives it (3 322).
+// PTGS_PT_ULOOP: the node loop's test `node >= 0 && node != DONE` as one unsigned compare. It rests on: a leaf
+// link has bit 31 set, so as unsigned it is above DONE (0x7fffffff, less the key's bits in the culling walk);
+// and DONE is above every interior index (bvh.cpp stack_layout sizes the link's bits for the node count, and
+// the key takes only what they leave). On: C3 6 529 -> 6 548 Mrays/s (+0.3%), C5's mesh 3 266 -> 3 322 (+1.7%).
+// In trace_any it leaves the shadow node step at 165 instructions.
+#ifndef PTGS_PT_ONE_POP
+#define PTGS_PT_ONE_POP 0
+#endif
+#ifndef PTGS_PT_ULOOP
+#define PTGS_PT_ULOOP 1
+#endif
+#ifndef PTGS_PT_ULOOP_ANY  // the same test in trace_any's single-exit walk
+#define PTGS_PT_ULOOP_ANY PTGS_PT_ULOOP
 #endif
 template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF, bool N64 = false, bool CULL = false>
 __device__ __forceinline__ Hit trace_closest(const DevScene& sc, const Ray& r, uint32_t seed, int* stack,
@@ -540,22 +631,65 @@ __device__ __forceinline__ Hit trace_closest(const DevScene& sc, const Ray& r, u
     } while (stack_bound(x, kmask) > cap);
     return (int)stack_link(x, kmask);
   };
+  // PTGS_PT_ONE_POP=1: pop(), and while the popped word is a leaf and the lane holds none, park it and pop again
+  auto pop_park = [&]() -> int {
+    const float cap = h.t * 1.0000004f;
+    int n;
+    bool again;
+    do {
+      uint32_t x = (uint32_t)DONE;
+      if (sp) {
+        --sp;
+        x = (uint32_t)((OVF == 0 || sp < PTGS_STACK) ? stack[sp * SS] : ovf[sp - PTGS_STACK]);
+      }
+      n = CULL ? (int)stack_link(x, kmask) : (int)x;
+      again = CULL && stack_bound(x, kmask) > cap;
+      if (!again && n < 0 && leaf == DONE) {
+        leaf = n;
+        again = true;
+      }
+    } while (again);
+    return n;
+  };
   // (a register-cached stack top that hides the LDS read behind the node fetch measured -0.8%)
   for (;;) {
+#if PTGS_PT_ULOOP
+    while ((uint32_t)node < (uint32_t)DONE) {
+#else
     while (node >= 0 && node != DONE) {
+#endif
       PT_LANE_TICK(cnt, PT_L_NODE);
       Box4 b;
       box4_sel<N64>(rq, sc, node, h.t, b);
       if (STATS) cnt.nodes += 4;
+#if PTGS_PT_ONE_POP
+      bool need = !__builtin_amdgcn_inverse_ballot_w64(b.hm[0] | b.hm[1] | b.hm[2] | b.hm[3]);
+      if (!need) {
+        node = enter_box4_hit(b, push);
+        if (node < 0 && leaf == DONE) {
+          leaf = node;
+          need = true;
+        }
+      }
+      if (need) node = PTGS_PT_ONE_POP == 1 ? pop_park() : pop();
+#else
       node = enter_box4(b, push, pop);
       if (node < 0 && leaf == DONE) {
         leaf = node;
         node = pop();
       }
+#endif
       // (every active lane holds a leaf or is done: the compares' lane mask against exec, no VGPR round trip)
+#if PTGS_PT_ONE_POP == 2
+      // (or holds in `node` a leaf it popped: it leaves the loop at the test above)
+      if ((__builtin_amdgcn_ballot_w64(leaf != DONE) | __builtin_amdgcn_ballot_w64((uint32_t)node >= (uint32_t)DONE)) ==
+          __builtin_amdgcn_read_exec())
+        break;
+#else
       if ((__builtin_amdgcn_ballot_w64(leaf != DONE) | __builtin_amdgcn_ballot_w64(node == DONE)) ==
           __builtin_amdgcn_read_exec())
         break;
+#endif
     }
     if (leaf != DONE) {
       PT_LANE_TICK(cnt, PT_L_LEAF);
@@ -678,7 +812,11 @@ __device__ __forceinline__ bool trace_any(const DevScene& sc, const Ray& r, uint
   };
   int leaf = DONE;  // (PARK: the postponed leaf)
   for (;;) {
+#if PTGS_PT_ULOOP_ANY
+    while ((uint32_t)node < (uint32_t)DONE) {  // (as trace_closest)
+#else
     while (node >= 0 && node != DONE) {
+#endif
       PT_LANE_TICK(cnt, PT_L_ANY_NODE);
       Box4 b;
       box4_sel<N64>(rq, sc, node, r.tmax, b);

@@ -11,6 +11,19 @@ build.build(defines=("PTGS_PT_ANY_SINGLE_EXIT=0",), variant="anyold") (the walk 
 scalar hit masks, and the postponed leaf), then `tools/ab_pt.py anyold base anypark` (base: single exit without the
 postponed leaf). The shadow leaf's switches likewise: PTGS_PT_ANY_TRI_FOLD=0, PTGS_PT_ANY_TRI_PREFETCH=1.
 
+The node step's switches (profiles/r10_summary.md), one row each, every one with all three defines spelled out so
+that a row does not move when a default does:
+  variant   PTGS_PT_PK_SLAB  PTGS_PT_ONE_POP  PTGS_PT_ULOOP
+  par       0                0                0              the step before
+  a         1                0                0              packed slab FMAs (afma: and PTGS_PT_PK_SLAB_MUL=0)
+  ab1, ab2  1                1, 2             0              + one pop site, parking (1) or popping once (2)
+  b1, b2    0                1, 2             0              one pop site without the packed FMAs
+  c         0                0                1              the unsigned loop test alone (the default build)
+  b1c, b2c  0                1, 2             1
+`tools/ab_pt.py par a ab1 ab2 b1 b2 c b1c b2c`; the C5 mesh and the viewer rows for the kept combination:
+`AB_SCENE=c5 tools/ab_pt.py par base`, `AB_SPP=1 AB_CALLS=64 tools/ab_pt.py par base`. A variant built with other
+compiler flags (round 10's rows with and without the SLP vectoriser) sets build.EXTRA before build.build.
+
 AB_SCENE=c5 times C5's mesh instead (the 1M-triangle atrium at 3840x2160, whose tree launches the DEEP
 kernels and whose nodes exceed an XCD's L2); AB_SPP, AB_ROUNDS, AB_CALLS as before. Each variant's image is
 compared with the first variant's first image.

@@ -7,7 +7,7 @@ Compiles csrc/<ISA_SRC> (default pt_kernels.hip) for the device only with build.
 defines, to assembly, and lists every loop (a backward branch to a label) of the kernel whose mangled name
 starts with ISA_KERNEL (default: the timed pt_camera_kernel<false, false, false>), nested by containment:
 all instructions, VALU, SALU (s_waitcnt and branches included), v_cvt_f32_ubyte (24 mark a compact-node box
-test), LDS, vector-memory loads and scratch accesses between the loop's header and its back edge. Then the
+test), pk (packed v_pk_ instructions: 12 v_pk_fma_f32 + 2 v_pk_mul_f32 mark a packed box test), LDS, vector-memory loads and scratch accesses between the loop's header and its back edge. Then the
 kernel's resource usage (-Rpass-analysis=kernel-resource-usage). The assembly is left in ISA_OUT (default: a
 temporary directory) as <ISA_TAG>.s.
 """
@@ -60,7 +60,7 @@ def main():
         n = lambda *p: sum(1 for x in ins if x.startswith(p))
         depth = sum(1 for c, d in loops if c <= a and d >= b) - 1
         print(f"{'  ' * depth}loop {a}-{b}: all {len(ins)} VALU {n('v_')} SALU {n('s_')} cvt_ubyte {n('v_cvt_f32_ubyte')} "
-              f"lds {n('ds_')} vmem_ld {n('global_load', 'buffer_load', 'flat_load')} scratch {n('scratch_')}")
+              f"pk {n('v_pk_')} lds {n('ds_')} vmem_ld {n('global_load', 'buffer_load', 'flat_load')} scratch {n('scratch_')}")
     show = False
     for l in r.stderr.split("\n"):
         if "Function Name:" in l:

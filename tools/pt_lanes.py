@@ -49,7 +49,8 @@ def main():
     print(f"{'loop':28s} {'wave iters (M)':>15s} {'lane iters (M)':>15s} {'per ray':>8s} {'utilisation':>12s}")
     for i, name in enumerate(LOOPS):
         w, l = int(buf[2 * i]), int(buf[2 * i + 1])
-        print(f"{name:28s} {w / 1e6:15.2f} {l / 1e6:15.2f} {l / max(rays, 1):8.2f} {l / max(64 * w, 1):12.3f}")
+        # (the raw counts last: two walks that visit the same nodes agree in them to the last digit)
+        print(f"{name:28s} {w / 1e6:15.2f} {l / 1e6:15.2f} {l / max(rays, 1):8.2f} {l / max(64 * w, 1):12.3f} {w:14d} {l:14d}")
     r.close()
 
 
