@@ -42,7 +42,9 @@ extern "C" {
                              * ptgs_gaussians_densify_plan, ptgs_gaussians_densify_apply (with their three
                              * structs), ptgs_image_loss_l1_dssim, ptgs_gaussians_adam_step,
                              * ptgs_gaussians_opacity_reset (with the structs ptgs_adam_rows and
-                             * ptgs_adam_params); ptgs_read_gaussian_ply in ptgs_host.h */
+                             * ptgs_adam_params), ptgs_splat_gaussians_invdepth,
+                             * ptgs_splat_gaussians_backward_depth, ptgs_image_loss_invdepth_l1;
+                             * ptgs_read_gaussian_ply in ptgs_host.h */
 
 /* ---------------- error codes ---------------- */
 #define PTGS_OK 0
@@ -710,6 +712,34 @@ int ptgs_splat_gaussians_backward(ptgs_ctx* ctx, const ptgs_gaussians* g, const 
                                   const float* dL_dout_rgba32f, const ptgs_gaussian_grads* grads,
                                   void* hip_stream);
 
+/* Depth supervision (the trainer's L1 on rendered inverse depth). ptgs_splat_gaussians_invdepth renders the
+ * expected inverse depth of the frame the context's latest ptgs_splat_gaussians published:
+ *   D[pixel] = sum alpha T / d   over the pixel's list, with the alpha, the skip, the clamp and the stop of the
+ *   function stated above and d = -(view * mean).z, the depth the rasterizer sorts by; no background term
+ * out_invdepth: device W*H floats; every pixel is written (0 where the tile's list is empty). The frame must meet
+ * the conditions of ptgs_splat_gaussians_backward (full-frame, published, with stats, the same width and height);
+ * the call only reads it and is not a splat call: the frame stays valid, so it can sit between the forward and
+ * the backward. The decisions are taken from z evaluated at (dx, dy) = pixel - means2d, as the backward takes
+ * them. Stream-ordered, no host wait, allocates nothing, no atomics: two runs give the same bits.
+ * PTGS_EINVAL (message in ptgs_last_error, nothing enqueued): a null ctx or out_invdepth, out_invdepth not a
+ * device pointer, no matching published frame.
+ *
+ * ptgs_splat_gaussians_backward_depth is ptgs_splat_gaussians_backward for a loss that depends on both out and
+ * D, in one pass: dL_dinvdepth (device, W*H) is dL/dD. The function being differentiated gains one sentence:
+ *   D = sum alpha T / d with the same alpha and T, every discrete decision held fixed as before
+ * so D passes gradient to the opacity, the conic and the 2D mean of a Gaussian through alpha and T exactly as a
+ * fourth colour channel of value 1 / d with background 0 would, and to the mean through 1 / d,
+ * d = -(view row 2) . (mean, 1). The depth still carries no gradient through order or membership; grads.colors
+ * does not depend on dL_dinvdepth. Contract, outputs and error paths are those of ptgs_splat_gaussians_backward
+ * (scratch: 10 floats per Gaussian), plus PTGS_EINVAL for a null or non-device dL_dinvdepth.
+ * Not covered: depth for _over, _views and tile-row shards, expected (non-inverse) or median depth, normals. */
+int ptgs_splat_gaussians_invdepth(ptgs_ctx* ctx, uint32_t width, uint32_t height, float* out_invdepth,
+                                  void* hip_stream);
+int ptgs_splat_gaussians_backward_depth(ptgs_ctx* ctx, const ptgs_gaussians* g, const ptgs_ubo* ubo,
+                                        uint32_t width, uint32_t height, const float bg[3],
+                                        const float* dL_dout_rgba32f, const float* dL_dinvdepth,
+                                        const ptgs_gaussian_grads* grads, void* hip_stream);
+
 /* Densification and pruning of a training run (densify_and_prune of Kerbl et al.'s trainer, new Gaussians
  * inheriting the parent's screen radius), in three steps: a statistic accumulated after every backward, a
  * plan (decision per Gaussian + scan) and one gather that writes the new arrays. Every float operation is an
@@ -823,6 +853,25 @@ int ptgs_gaussians_densify_apply(ptgs_ctx* ctx, uint32_t n, uint32_t n_out, cons
 int ptgs_image_loss_l1_dssim(ptgs_ctx* ctx, const float* image_rgba32f, const float* target,
                              uint32_t target_channels, uint32_t width, uint32_t height, float lambda,
                              float grad_scale, float* loss_out, float* dL_dimage_rgba32f, void* hip_stream);
+
+/* The trainer's depth regulariser: an L1 between a rendered inverse depth (ptgs_splat_gaussians_invdepth) and a
+ * target given as a VIEW DEPTH map t, as ptgs_trace_depth writes it (both device, W*H floats). A pixel is
+ * supervised when t > 0; that includes +inf (a miss), whose target inverse depth is 0. A pixel with t <= 0 or a
+ * NaN t is not supervised: it adds 0 to the loss and gets gradient 0.
+ *   term = |D - 1.0f / t|                      f32, IEEE divide, no contraction
+ *   sum  = the f64 sum of the terms in a fixed order (per workgroup, then one final workgroup)
+ *   terms = (weight * sum / (W H), sum / (W H), number of supervised pixels, 0)      device float[4], rounded to f32
+ *   dL/dD = k * sign(D - 1.0f / t), sign(0) = 0, k = (float)((double)weight * grad_scale / (W H))
+ * The mean is over all W H pixels (the trainer's .mean() of the masked difference). dL_dinvdepth: device W*H,
+ * every element overwritten, or NULL: only the terms (bit for bit those of a call with the gradient). No atomics:
+ * two calls give the same bits. Stream-ordered, no host wait; the per-workgroup sums live in the context's loss
+ * workspace, which grows on demand as for ptgs_image_loss_l1_dssim.
+ * PTGS_EINVAL (message in ptgs_last_error, nothing enqueued): a null ctx, invdepth, target_depth or terms; width
+ * or height 0 or above 16384; weight or grad_scale not finite; dL_dinvdepth overlapping invdepth or target_depth;
+ * invdepth, target_depth, terms or dL_dinvdepth not a device pointer. */
+int ptgs_image_loss_invdepth_l1(ptgs_ctx* ctx, const float* invdepth, const float* target_depth, uint32_t width,
+                                uint32_t height, float weight, float grad_scale, float* terms,
+                                float* dL_dinvdepth, void* hip_stream);
 
 /* The optimizer step of a training run: Adam (Kingma & Ba; no weight decay, no amsgrad) over every per-Gaussian
  * parameter array in one launch, optionally skipping the Gaussians the view did not see (the `sparse_adam` of

@@ -266,12 +266,16 @@ SYMBOLS = {
     "ptgs_gaussians_permute_sh": (_I, [_P, _P, _U, _P, _U, _P, _P]),
     "ptgs_splat_gaussians_backward": (_I, [_P, C.POINTER(Gaussians), C.POINTER(Ubo), _U, _U, _FP, _P,
                                            C.POINTER(GaussianGrads), _P]),
+    "ptgs_splat_gaussians_invdepth": (_I, [_P, _U, _U, _P, _P]),
+    "ptgs_splat_gaussians_backward_depth": (_I, [_P, C.POINTER(Gaussians), C.POINTER(Ubo), _U, _U, _FP, _P, _P,
+                                                 C.POINTER(GaussianGrads), _P]),
     "ptgs_densify_accumulate": (_I, [_P, _P, _P, _U, _U, _U, _P, _P, _P, _P]),
     "ptgs_gaussians_densify_plan": (_I, [_P, _P, _P, _P, _P, _P, _U, C.POINTER(DensifyParams),
                                          C.POINTER(DensifyCounts), _P]),
     "ptgs_gaussians_densify_apply": (_I, [_P, _U, _U, _P, _P, _P, _P, _P, _P, _P, C.POINTER(DensifyRows), _U, _P,
                                           _P]),
     "ptgs_image_loss_l1_dssim": (_I, [_P, _P, _P, _U, _U, _U, C.c_float, C.c_float, _P, _P, _P]),
+    "ptgs_image_loss_invdepth_l1": (_I, [_P, _P, _P, _U, _U, C.c_float, C.c_float, _P, _P, _P]),
     "ptgs_gaussians_adam_step": (_I, [_P, _U, C.POINTER(AdamRows), _U, C.POINTER(AdamParams), _P, _P]),
     "ptgs_gaussians_opacity_reset": (_I, [_P, _P, _U, C.c_float, _P, _P, _P]),
     "ptgs_trace_depth_rows": (_I, [_P, C.POINTER(Ubo), _U, _U, _U, _U, _P, _P]),

@@ -1047,11 +1047,12 @@ int ptgs_gaussians_permute_sh(ptgs_ctx* c, const float* sh, uint32_t sh_degree, 
   return hip_rc(c, e, "ptgs_gaussians_permute_sh");
 }
 
-int ptgs_splat_gaussians_backward(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t w, uint32_t h,
-                                  const float bg[3], const float* dL_dout, const ptgs_gaussian_grads* grads,
-                                  void* stream) {
+// ptgs_splat_gaussians_backward (depth == false: dL_dinvdepth is not looked at) and _backward_depth
+static int splat_backward_call(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t w, uint32_t h,
+                               const float bg[3], const float* dL_dout, bool depth, const float* dL_dinvdepth,
+                               const ptgs_gaussian_grads* grads, void* stream, const char* name) {
   if (!c) return PTGS_EINVAL;
-  if (!g || !ubo || !bg || !dL_dout || !grads) return fail(c, PTGS_EINVAL, "null argument");
+  if (!g || !ubo || !bg || !dL_dout || !grads || (depth && !dL_dinvdepth)) return fail(c, PTGS_EINVAL, "null argument");
   if (g->ids) return fail(c, PTGS_EINVAL, "the backward pass takes the Gaussians in their original order (ids must be NULL)");
   if (g->count == 0) return PTGS_OK;  // (empty arrays may be null)
   if (!g->means || !g->scales || !g->rotations || !g->opacities || !g->colors)
@@ -1060,6 +1061,7 @@ int ptgs_splat_gaussians_backward(ptgs_ctx* c, const ptgs_gaussians* g, const pt
     return fail(c, PTGS_EINVAL, "null gradient array (means2d and conics alone are optional)");
   if (!is_device_ptr(dL_dout) || !is_device_ptr(grads->means))
     return fail(c, PTGS_EINVAL, "dL_dout / gradient arrays must be device pointers");
+  if (depth && !is_device_ptr(dL_dinvdepth)) return fail(c, PTGS_EINVAL, "dL_dinvdepth must be a device pointer");
   if (ubo->proj[0] == 0.0f || ubo->proj[5] == 0.0f) return fail(c, PTGS_EINVAL, "degenerate projection");
   SplatFrame f;
   splat_last_frame(c->frames.current(), &f);
@@ -1072,12 +1074,42 @@ int ptgs_splat_gaussians_backward(ptgs_ctx* c, const ptgs_gaussians* g, const pt
                 f.H, g->count, w, h);
   HIPCHK(c, hipSetDevice(c->device));
   float* acc = nullptr;
-  HIPCHK(c, splat_backward_scratch(c->frames.current(), f.n, &acc));
+  HIPCHK(c, splat_backward_scratch(c->frames.current(), f.n, depth ? GS_BWD_ACC_DEPTH : GS_BWD_ACC, &acc));
   float mvp[16];
   mat4_mul(ubo->proj, ubo->view, mvp);
-  const hipError_t e = splat_gaussians_backward(f, acc, g, ubo->view, mvp, ubo->proj[0], ubo->proj[5], bg, dL_dout, grads,
-                                                (hipStream_t)stream);
-  return hip_rc(c, e, "ptgs_splat_gaussians_backward");
+  const hipError_t e = splat_gaussians_backward(f, acc, g, ubo->view, mvp, ubo->proj[0], ubo->proj[5], bg, dL_dout,
+                                                depth ? dL_dinvdepth : nullptr, grads, (hipStream_t)stream);
+  return hip_rc(c, e, name);
+}
+
+int ptgs_splat_gaussians_backward(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t w, uint32_t h,
+                                  const float bg[3], const float* dL_dout, const ptgs_gaussian_grads* grads,
+                                  void* stream) {
+  return splat_backward_call(c, g, ubo, w, h, bg, dL_dout, false, nullptr, grads, stream, "ptgs_splat_gaussians_backward");
+}
+
+int ptgs_splat_gaussians_backward_depth(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t w,
+                                        uint32_t h, const float bg[3], const float* dL_dout, const float* dL_dinvdepth,
+                                        const ptgs_gaussian_grads* grads, void* stream) {
+  return splat_backward_call(c, g, ubo, w, h, bg, dL_dout, true, dL_dinvdepth, grads, stream,
+                             "ptgs_splat_gaussians_backward_depth");
+}
+
+int ptgs_splat_gaussians_invdepth(ptgs_ctx* c, uint32_t w, uint32_t h, float* out_invdepth, void* stream) {
+  if (!c) return PTGS_EINVAL;
+  if (!out_invdepth) return fail(c, PTGS_EINVAL, "null argument");
+  if (!is_device_ptr(out_invdepth)) return fail(c, PTGS_EINVAL, "out_invdepth must be a device pointer");
+  SplatFrame f;
+  splat_last_frame(c->frames.current(), &f);
+  if (!f.valid)
+    return fail(c, PTGS_EINVAL,
+                "no frame to render the inverse depth of: the latest splat call must be a full-frame "
+                "ptgs_splat_gaussians with PTGS_FLAG_SPLAT_PUBLISH and stats");
+  if (f.W != w || f.H != h)
+    return fail(c, PTGS_EINVAL, "the latest frame is %ux%u, the inverse-depth call %ux%u", f.W, f.H, w, h);
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipError_t e = splat_gaussians_invdepth(f, out_invdepth, (hipStream_t)stream);
+  return hip_rc(c, e, "ptgs_splat_gaussians_invdepth");
 }
 
 // An array of a call as a byte range (densify apply, Adam step); out: the call writes it.
@@ -1200,6 +1232,30 @@ int ptgs_image_loss_l1_dssim(ptgs_ctx* c, const float* image, const float* targe
   const hipError_t e = image_loss_l1_dssim(c->loss, image, target, target_channels, w, h, lambda, grad_scale, loss_out,
                                            dL_dimage, (hipStream_t)stream);
   return hip_rc(c, e, "ptgs_image_loss_l1_dssim");
+}
+
+int ptgs_image_loss_invdepth_l1(ptgs_ctx* c, const float* invdepth, const float* target_depth, uint32_t w, uint32_t h,
+                                float weight, float grad_scale, float* terms, float* dL_dinvdepth, void* stream) {
+  if (!c) return PTGS_EINVAL;
+  if (!invdepth || !target_depth || !terms) return fail(c, PTGS_EINVAL, "null argument");
+  if (w == 0 || h == 0 || w > LOSS_MAX_SIDE || h > LOSS_MAX_SIDE)
+    return fail(c, PTGS_EINVAL, "map of %u x %u: each side is 1 .. %u", w, h, LOSS_MAX_SIDE);
+  if (!std::isfinite(weight)) return fail(c, PTGS_EINVAL, "weight must be finite");
+  if (!std::isfinite(grad_scale)) return fail(c, PTGS_EINVAL, "grad_scale must be finite");
+  if (dL_dinvdepth) {
+    const char *g = (const char*)dL_dinvdepth, *a = (const char*)invdepth, *b = (const char*)target_depth;
+    const size_t bytes = (size_t)w * h * sizeof(float);
+    if ((g < a + bytes && a < g + bytes) || (g < b + bytes && b < g + bytes))
+      return fail(c, PTGS_EINVAL, "dL_dinvdepth overlaps invdepth or target_depth");
+    if (!is_device_ptr(dL_dinvdepth)) return fail(c, PTGS_EINVAL, "dL_dinvdepth is not a device pointer");
+  }
+  if (!is_device_ptr(invdepth) || !is_device_ptr(target_depth))
+    return fail(c, PTGS_EINVAL, "invdepth / target_depth must be device pointers");
+  if (!is_device_ptr(terms)) return fail(c, PTGS_EINVAL, "terms is not a device pointer");
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipError_t e = image_loss_invdepth_l1(c->loss, invdepth, target_depth, w, h, weight, grad_scale, terms,
+                                              dL_dinvdepth, (hipStream_t)stream);
+  return hip_rc(c, e, "ptgs_image_loss_invdepth_l1");
 }
 
 int ptgs_gaussians_adam_step(ptgs_ctx* c, uint32_t n, const ptgs_adam_rows* rows, uint32_t n_rows,

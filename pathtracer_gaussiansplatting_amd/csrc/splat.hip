@@ -677,8 +677,8 @@ void splat_last_frame(const SplatWorkspace* w, SplatFrame* out) {
   out->radii = (const int*)w->radii.p;
 }
 
-hipError_t splat_backward_scratch(SplatWorkspace* w, uint32_t n, float** acc) {
-  const hipError_t e = ensure(w->grad_acc, (size_t)n * GS_BWD_ACC * 4);
+hipError_t splat_backward_scratch(SplatWorkspace* w, uint32_t n, uint32_t floats_per_gaussian, float** acc) {
+  const hipError_t e = ensure(w->grad_acc, (size_t)n * floats_per_gaussian * 4);
   *acc = (float*)w->grad_acc.p;
   return e;
 }

@@ -24,12 +24,18 @@ void splat_last_frame(const SplatWorkspace* w, SplatFrame* out);
 // the backward's per-Gaussian accumulator (GS_BWD_ACC floats per Gaussian; grown like the other
 // workspace buffers: growth frees the old one, which waits for the device)
 #define GS_BWD_ACC 9
-hipError_t splat_backward_scratch(SplatWorkspace* w, uint32_t n, float** acc);
+#define GS_BWD_ACC_DEPTH 10  // with dL/d(1/d): the backward that also takes dL/d(inverse depth)
+hipError_t splat_backward_scratch(SplatWorkspace* w, uint32_t n, uint32_t floats_per_gaussian, float** acc);
 
 // view/mvp column-major float[16]; p00 = proj[0][0], p11 = proj[1][1]; f: the frame (splat_last_frame,
-// valid), acc: splat_backward_scratch(n). Stream-ordered on s.
+// valid), acc: splat_backward_scratch(n, GS_BWD_ACC), or (n, GS_BWD_ACC_DEPTH) with dL_dinvdepth (W*H floats,
+// the gradient with respect to splat_gaussians_invdepth's output; null: the loss depends on the image alone).
+// Stream-ordered on s.
 hipError_t splat_gaussians_backward(const SplatFrame& f, float* acc, const ptgs_gaussians* g, const float* view,
                                     const float* mvp, float p00, float p11, const float bg[3], const float* dL_dout,
-                                    const ptgs_gaussian_grads* grads, hipStream_t s);
+                                    const float* dL_dinvdepth, const ptgs_gaussian_grads* grads, hipStream_t s);
+// out[W*H] = the frame's expected inverse depth, sum alpha T / d per pixel (no background term). Reads the
+// frame only: it stays valid. Stream-ordered on s; no atomics.
+hipError_t splat_gaussians_invdepth(const SplatFrame& f, float* out, hipStream_t s);
 
 }  // namespace ptgs

@@ -21,6 +21,13 @@
 //                       and, through conic = cov^-1, cov = T Sigma T^T + 0.3 I, T = J W, Sigma = R S^2 R^T,
 //                       q / |q|, the 3D mean, the scales and the rotation. Plain f32.
 // Float atomics: the sums depend on the arrival order, so the gradients are not bit-reproducible.
+//
+// Depth supervision rides in the same walks. The expected inverse depth D = sum alpha T / d of a pixel is
+// formally a fourth colour channel (1 / d per Gaussian, d the record's view depth, background 0):
+//   gs_invdepth_kernel (ptgs_splat_gaussians_invdepth) renders it with the blend backward's first walk;
+//   both backward kernels are templated on DEPTH (ptgs_splat_gaussians_backward_depth): the blend adds
+//   (1 / d) dL/dD to c . dL/dC and a tenth sum, dL/d(1/d); the projection carries that to the mean through d.
+// The DEPTH = false instantiations are the kernels as they were.
 #include <hip/hip_runtime.h>
 
 #include "../../include/ptgs/ptgs.h"
@@ -34,9 +41,13 @@ namespace ptgs {
 #define GB_TILE 16
 #define GB_CHUNK 64  // staged pairs per reduction round: a wave's ballot; 23 KiB of LDS, 7 waves per SIMD (256:
                      // 50 KiB, 3 waves per SIMD, 0.50 vs 0.37 ms at C2)
+#ifndef GB_CHUNK_DEPTH
+#define GB_CHUNK_DEPTH GB_CHUNK  // the same for the kernel with the inverse-depth sum (10 sums per pair)
+#endif
 #define GB_L2E 1.4426950408889634f
 #define GB_LN2 0.69314718055994531f
 static_assert(GS_BWD_ACC == 9, "2D mean x2, staged quadratic A B C, log2 opacity, colour x3");
+static_assert(GS_BWD_ACC_DEPTH == GS_BWD_ACC + 1, "and 1 / d");
 
 // Wave64 float sum in DPP (row_shr 1/2/4/8 inside rows of 16, then row_bcast 15 / 31): lane 63 ends with
 // the sum of all 64, returned wave-uniform. Every lane of the wave must be active.
@@ -51,17 +62,86 @@ __device__ __forceinline__ float gb_wave_sum(float v) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
-// acc: per Gaussian (d gx, d gy, dA, dB, dC, dL, d r, d g, d b) for the staged z = A dx^2 + B dx dy +
+// One batch of a tile's list into LDS: work-item tid stages pair base + tid (records, Gaussian ids, quadrant
+// masks). INVD: the free fourth word of the third stage entry holds 1 / d (d: the record's view depth, the
+// forward's sort key), computed once per staged record; otherwise it is 0. GID: the ids are staged (s_gid).
+template <bool INVD, bool GID>
+__device__ __forceinline__ void gb_stage_batch(uint32_t tid, uint32_t idx, uint32_t n, uint32_t first,
+                                               const uint32_t* vals, const float4* rec, float tx0, float ty0,
+                                               float4* s_stage, uint32_t* s_gid, uint8_t* s_mask) {
+  if (idx < n) {
+    const uint32_t g = vals[first + idx];
+    const float4 ga = rec[3 * g], gb = rec[3 * g + 1], gc = rec[3 * g + 2];
+    // the record's quadratic and the 2D mean in tile-local pixel coordinates. z is evaluated from
+    // (dx, dy) = pixel - mean, as ptgs.h states the function, not from the forward's expansion into
+    // A ux^2 + ... + F: there terms of several hundred cancel to a z of a few units, an error of 3e-5
+    // in alpha that the forward's 1e-4 allowance covers but that reached 1.5e-4 relative L2 in the
+    // gradients of the quarter of a case's Gaussians with the smallest ones (5e-6, float32 autograd's
+    // own error there, in this form)
+    const float gx = ga.x - tx0, gy = ga.y - ty0;
+    s_stage[3 * tid] = make_float4(ga.z, ga.w, gb.x, gb.y);
+    s_stage[3 * tid + 1] = make_float4(0.0f, 0.0f, gb.z, gb.w);
+    s_stage[3 * tid + 2] = make_float4(gc.x, gx, gy, INVD ? 1.0f / gc.w : 0.0f);
+    if (GID) s_gid[tid] = g;
+    // the forward's quadrant mask of the record's alpha box (gc.y, gc.z: the half-extents outside
+    // which alpha < 1/255): bit q = (x half q & 1, y half q >> 1), wave q's pixels
+    const float x0 = gx - gc.y, x1 = gx + gc.y, y0 = gy - gc.z, y1 = gy + gc.z;
+    const bool xl = x0 <= 7.0f && x1 >= 0.0f, xr = x0 <= 15.0f && x1 >= 8.0f;
+    const bool yt = y0 <= 7.0f && y1 >= 0.0f, yb = y0 <= 15.0f && y1 >= 8.0f;
+    s_mask[tid] = (uint8_t)((uint32_t)(xl && yt) | ((uint32_t)(xr && yt) << 1) | ((uint32_t)(xl && yb) << 2) |
+                            ((uint32_t)(xr && yb) << 3));
+  }
+}
+
+// The front-to-back walk of a chunk [c0, c1) of the staged batch by one wave, the part that the backward's two
+// walks and the inverse-depth render share. gb_walk_begin: the chunk's pairs whose alpha box reaches the
+// wave's quadrant (a ballot of the masks; the walk takes them in sorted order, lowest bit first).
+// gb_walk_z: z of a staged record at (dx, dy) = pixel - mean; a lane evaluates the pair when
+// z >= GB_Z_SKIP (alpha >= 1/255) and it has not stopped. gb_walk_pair: alpha with the 0.99 clamp (0 for a
+// lane that does not evaluate the pair), wgt = alpha T, and next_T = T - wgt; the pixel stops before a pair
+// whose next_T < GB_T_STOP. (That test and its four assignments stay in the kernels: inside this function they
+// cost the backward kernel two VGPRs.)
+#define GB_Z_SKIP (-7.9943534f)
+#define GB_T_STOP 0.0001f
+__device__ __forceinline__ unsigned long long gb_walk_begin(const uint8_t* s_mask, uint32_t c0, uint32_t c1,
+                                                            uint32_t wave, uint32_t lane) {
+  return __builtin_amdgcn_ballot_w64(c0 + lane < c1 && ((s_mask[c0 + lane] >> wave) & 1u));
+}
+
+__device__ __forceinline__ float gb_walk_z(const float4& a, float dx, float dy) {
+  return __builtin_fmaf(a.x * dx, dx, __builtin_fmaf(a.y * dx, dy, __builtin_fmaf(a.z * dy, dy, a.w)));
+}
+
+struct GbPair {
+  float alpha, wgt, next_T;
+};
+
+__device__ __forceinline__ GbPair gb_walk_pair(float e, bool valid, float T) {
+  GbPair p;
+  p.alpha = valid ? fminf(0.99f, e) : 0.0f;
+  p.wgt = p.alpha * T;
+  p.next_T = T - p.wgt;
+  return p;
+}
+
+// acc: per Gaussian (d gx, d gy, dA, dB, dC, dL, d r, d g, d b[, d (1/d)]) for the staged z = A dx^2 + B dx dy +
 // C dy^2 + L (dx, dy: pixel - 2D mean; A = -a/2 log2e, B = -b log2e, C = -c/2 log2e, L = log2 o).
+// DEPTH: the loss also depends on the inverse depth D = sum wgt / d (gs_invdepth_kernel), formally a fourth
+// colour channel 1 / d with background 0 and upstream gradient dinv: it joins c . dL/dC, and a tenth sum
+// (wgt dinv = dL/d(1/d)) joins the accumulator.
+template <bool DEPTH>
 __global__ __launch_bounds__(GB_BLOCK) void gs_blend_backward_kernel(uint32_t W, uint32_t H, uint32_t grid_x,
                                                                       const uint2* __restrict__ ranges,
                                                                       const uint32_t* __restrict__ vals,
                                                                       const float4* __restrict__ rec, float bg_r,
                                                                       float bg_g, float bg_b,
                                                                       const float4* __restrict__ dout,
+                                                                      const float* __restrict__ dinv,
                                                                       float* __restrict__ acc) {
-  __shared__ float4 s_stage[3 * GB_BLOCK];  // (A, B, C, L) (-, -, r, g) (b, gx, gy, -): the record, mean tile-local
-  __shared__ __attribute__((aligned(16))) float s_red[4][GB_CHUNK * GS_BWD_ACC];  // per wave, per pair of a chunk
+  constexpr uint32_t ACC = DEPTH ? GS_BWD_ACC_DEPTH : GS_BWD_ACC, CHUNK = DEPTH ? GB_CHUNK_DEPTH : GB_CHUNK;
+  static_assert(CHUNK <= 64 && (CHUNK * ACC) % 4 == 0, "a chunk is one ballot; its sums are cleared as float4");
+  __shared__ float4 s_stage[3 * GB_BLOCK];  // (A, B, C, L) (-, -, r, g) (b, gx, gy, 1/d): the record, mean tile-local
+  __shared__ __attribute__((aligned(16))) float s_red[4][CHUNK * ACC];  // per wave, per pair of a chunk
   __shared__ uint32_t s_gid[GB_BLOCK];
   __shared__ uint8_t s_mask[GB_BLOCK];
   const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
@@ -74,8 +154,9 @@ __global__ __launch_bounds__(GB_BLOCK) void gs_blend_backward_kernel(uint32_t W,
   const uint32_t py = tile_y * GB_TILE + (wave >> 1) * 8u + (lane >> 3);
   const bool inside = px < W && py < H;
   const float4 go = inside ? dout[(size_t)py * W + px] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  const float gd = (DEPTH && inside) ? dinv[(size_t)py * W + px] : 0.0f;
   const float ux = (float)px - tx0, uy = (float)py - ty0;
-  // out.rgb = C + T_final bg, out.a = 1 - T_final: dL/dT_final
+  // out.rgb = C + T_final bg, out.a = 1 - T_final: dL/dT_final (D has no background term)
   const float g_tf = ((go.x * bg_r + go.y * bg_g) + go.z * bg_b) - go.w;
   // sum over the pixel's pairs of wgt (c . dL/dC), + T_final dL/dT_final. It and its running prefix are f64
   // sums of the f32 terms: what lies behind a pair is their difference, and deep in a list (T small) that is
@@ -89,62 +170,41 @@ __global__ __launch_bounds__(GB_BLOCK) void gs_blend_backward_kernel(uint32_t W,
     for (uint32_t base = 0; base < n; base += GB_BLOCK) {
       // (every wave is done with the previous batch's records and sums)
       if (__syncthreads_count(done) == GB_BLOCK) break;
-      const uint32_t idx = base + tid;
-      if (idx < n) {
-        const uint32_t g = vals[range.x + idx];
-        const float4 ga = rec[3 * g], gb = rec[3 * g + 1], gc = rec[3 * g + 2];
-        // the record's quadratic and the 2D mean in tile-local pixel coordinates. z is evaluated from
-        // (dx, dy) = pixel - mean, as ptgs.h states the function, not from the forward's expansion into
-        // A ux^2 + ... + F: there terms of several hundred cancel to a z of a few units, an error of 3e-5
-        // in alpha that the forward's 1e-4 allowance covers but that reached 1.5e-4 relative L2 in the
-        // gradients of the quarter of a case's Gaussians with the smallest ones (5e-6, float32 autograd's
-        // own error there, in this form)
-        const float gx = ga.x - tx0, gy = ga.y - ty0;
-        s_stage[3 * tid] = make_float4(ga.z, ga.w, gb.x, gb.y);
-        s_stage[3 * tid + 1] = make_float4(0.0f, 0.0f, gb.z, gb.w);
-        s_stage[3 * tid + 2] = make_float4(gc.x, gx, gy, 0.0f);
-        s_gid[tid] = g;
-        // the forward's quadrant mask of the record's alpha box (gc.y, gc.z: the half-extents outside
-        // which alpha < 1/255): bit q = (x half q & 1, y half q >> 1), wave q's pixels
-        const float x0 = gx - gc.y, x1 = gx + gc.y, y0 = gy - gc.z, y1 = gy + gc.z;
-        const bool xl = x0 <= 7.0f && x1 >= 0.0f, xr = x0 <= 15.0f && x1 >= 8.0f;
-        const bool yt = y0 <= 7.0f && y1 >= 0.0f, yb = y0 <= 15.0f && y1 >= 8.0f;
-        s_mask[tid] = (uint8_t)((uint32_t)(xl && yt) | ((uint32_t)(xr && yt) << 1) | ((uint32_t)(xl && yb) << 2) |
-                                ((uint32_t)(xr && yb) << 3));
-      }
+      gb_stage_batch<DEPTH, true>(tid, base + tid, n, range.x, vals, rec, tx0, ty0, s_stage, s_gid, s_mask);
       __syncthreads();
       const uint32_t nb = min((uint32_t)GB_BLOCK, n - base);
-      // chunks of GB_CHUNK staged pairs: the wave walks the chunk's pairs whose box reaches its quadrant (a
-      // ballot of the masks, in sorted order), and the second walk reduces and sends its sums per chunk (the
-      // sums' LDS is what bounds the workgroups per CU)
-      for (uint32_t c0 = 0; c0 < nb; c0 += GB_CHUNK) {
-        const uint32_t c1 = min(nb, c0 + GB_CHUNK);
+      // chunks of CHUNK staged pairs: the wave walks the chunk's pairs whose box reaches its quadrant, and
+      // the second walk reduces and sends its sums per chunk (the sums' LDS is what bounds the workgroups per CU)
+      for (uint32_t c0 = 0; c0 < nb; c0 += CHUNK) {
+        const uint32_t c1 = min(nb, c0 + CHUNK);
         if (pass) {  // the wave's sums of this chunk start at zero: a pair it skips costs nothing more
           if (c0) __syncthreads();  // (the previous chunk's sums have been read)
           float4* z4 = reinterpret_cast<float4*>(s_red[wave]);
-          for (uint32_t k = lane; k < GB_CHUNK * GS_BWD_ACC / 4; k += 64) z4[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+          for (uint32_t k = lane; k < CHUNK * ACC / 4; k += 64) z4[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
-        unsigned long long todo = __builtin_amdgcn_ballot_w64(c0 + lane < c1 && ((s_mask[c0 + lane] >> wave) & 1u));
+        unsigned long long todo = gb_walk_begin(s_mask, c0, c1, wave, lane);
         while (todo) {
           if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;  // every pixel of the wave has stopped
           const uint32_t k = (uint32_t)__builtin_ctzll(todo), j = c0 + k;
           todo &= todo - 1ull;
           const float4 a = s_stage[3 * j], b = s_stage[3 * j + 1], c = s_stage[3 * j + 2];
           const float dx = ux - c.y, dy = uy - c.z;
-          const float z = __builtin_fmaf(a.x * dx, dx, __builtin_fmaf(a.y * dx, dy, __builtin_fmaf(a.z * dy, dy, a.w)));
-          bool valid = z >= -7.9943534f && !done;  // alpha >= 1/255
+          const float z = gb_walk_z(a, dx, dy);
+          bool valid = z >= GB_Z_SKIP && !done;  // alpha >= 1/255
           if (__builtin_amdgcn_ballot_w64(valid) == 0ull) continue;  // no lane of the wave evaluates the pair
           const float e = __builtin_amdgcn_exp2f(z);
-          const float alpha = valid ? fminf(0.99f, e) : 0.0f;
-          float wgt = alpha * T;
-          float test_T = T - wgt;
-          if (test_T < 0.0001f) {  // this Gaussian would saturate the pixel: stop before it
+          const GbPair p = gb_walk_pair(e, valid, T);
+          const float alpha = p.alpha;
+          float wgt = p.wgt;
+          float test_T = p.next_T;
+          if (test_T < GB_T_STOP) {  // this Gaussian would saturate the pixel: stop before it
             done = true;
             valid = false;
             wgt = 0.0f;
             test_T = T;
           }
-          const float cdot = (b.z * go.x + b.w * go.y) + c.x * go.z;
+          float cdot = (b.z * go.x + b.w * go.y) + c.x * go.z;
+          if (DEPTH) cdot += c.w * gd;
           if (!pass) {
             total += (double)(wgt * cdot);
           } else {
@@ -160,9 +220,11 @@ __global__ __launch_bounds__(GB_BLOCK) void gs_blend_backward_kernel(uint32_t W,
               const float s2 = gb_wave_sum(dz * dx * dx), s3 = gb_wave_sum(dz * dx * dy), s4 = gb_wave_sum(dz * dy * dy);
               const float s5 = gb_wave_sum(dz);
               const float s6 = gb_wave_sum(wgt * go.x), s7 = gb_wave_sum(wgt * go.y), s8 = gb_wave_sum(wgt * go.z);
+              const float s9 = DEPTH ? gb_wave_sum(wgt * gd) : 0.0f;
               if (lane == 63) {
-                float* r = &s_red[wave][k * GS_BWD_ACC];
+                float* r = &s_red[wave][k * ACC];
                 r[0] = s0; r[1] = s1; r[2] = s2; r[3] = s3; r[4] = s4; r[5] = s5; r[6] = s6; r[7] = s7; r[8] = s8;
+                if (DEPTH) r[9] = s9;
               }
             }
           }
@@ -172,11 +234,10 @@ __global__ __launch_bounds__(GB_BLOCK) void gs_blend_backward_kernel(uint32_t W,
           __syncthreads();
           // the four waves' sums, one atomic per value per (tile, Gaussian): consecutive lanes add the
           // consecutive values of a Gaussian; a value no pixel of the tile contributed to is not sent
-          for (uint32_t i = tid; i < (c1 - c0) * GS_BWD_ACC; i += GB_BLOCK) {
+          for (uint32_t i = tid; i < (c1 - c0) * ACC; i += GB_BLOCK) {
             const float s = (s_red[0][i] + s_red[1][i]) + (s_red[2][i] + s_red[3][i]);
-            const uint32_t slot = i / GS_BWD_ACC;
-            if (s != 0.0f)
-              (void)unsafeAtomicAdd(acc + (size_t)s_gid[c0 + slot] * GS_BWD_ACC + (i - slot * GS_BWD_ACC), s);
+            const uint32_t slot = i / ACC;
+            if (s != 0.0f) (void)unsafeAtomicAdd(acc + (size_t)s_gid[c0 + slot] * ACC + (i - slot * ACC), s);
           }
         }
       }
@@ -185,20 +246,74 @@ __global__ __launch_bounds__(GB_BLOCK) void gs_blend_backward_kernel(uint32_t W,
   }
 }
 
+// D[pixel] = sum over the pixel's pairs of wgt / d (ptgs_splat_gaussians_invdepth): the backward's first walk
+// with the staged 1 / d as the only colour and no background. One workgroup per tile, one pixel per lane; no
+// atomics, a fixed order: two runs are bit-equal. Every pixel inside the image is written (0 in an empty tile).
+__global__ __launch_bounds__(GB_BLOCK) void gs_invdepth_kernel(uint32_t W, uint32_t H, uint32_t grid_x,
+                                                                const uint2* __restrict__ ranges,
+                                                                const uint32_t* __restrict__ vals,
+                                                                const float4* __restrict__ rec,
+                                                                float* __restrict__ out) {
+  __shared__ float4 s_stage[3 * GB_BLOCK];
+  __shared__ uint8_t s_mask[GB_BLOCK];
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+  const uint32_t tile = blockIdx.x, tile_y = tile / grid_x, tile_x = tile - tile_y * grid_x;
+  const uint2 range = ranges[tile];
+  const uint32_t n = range.y - range.x;
+  const float tx0 = (float)(tile_x * GB_TILE), ty0 = (float)(tile_y * GB_TILE);
+  const uint32_t px = tile_x * GB_TILE + (wave & 1u) * 8u + (lane & 7u);
+  const uint32_t py = tile_y * GB_TILE + (wave >> 1) * 8u + (lane >> 3);
+  const bool inside = px < W && py < H;
+  const float ux = (float)px - tx0, uy = (float)py - ty0;
+  float T = 1.0f, D = 0.0f;
+  bool done = !inside;
+  for (uint32_t base = 0; base < n; base += GB_BLOCK) {
+    if (__syncthreads_count(done) == GB_BLOCK) break;  // (and: every wave is done with the previous batch)
+    gb_stage_batch<true, false>(tid, base + tid, n, range.x, vals, rec, tx0, ty0, s_stage, nullptr, s_mask);
+    __syncthreads();
+    const uint32_t nb = min((uint32_t)GB_BLOCK, n - base);
+    for (uint32_t c0 = 0; c0 < nb; c0 += GB_CHUNK) {
+      unsigned long long todo = gb_walk_begin(s_mask, c0, min(nb, c0 + GB_CHUNK), wave, lane);
+      while (todo) {
+        if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;  // every pixel of the wave has stopped
+        const uint32_t j = c0 + (uint32_t)__builtin_ctzll(todo);
+        todo &= todo - 1ull;
+        const float4 a = s_stage[3 * j], c = s_stage[3 * j + 2];
+        const float z = gb_walk_z(a, ux - c.y, uy - c.z);
+        const bool valid = z >= GB_Z_SKIP && !done;  // alpha >= 1/255
+        if (__builtin_amdgcn_ballot_w64(valid) == 0ull) continue;  // no lane of the wave evaluates the pair
+        const GbPair p = gb_walk_pair(__builtin_amdgcn_exp2f(z), valid, T);
+        float wgt = p.wgt, test_T = p.next_T;
+        if (test_T < GB_T_STOP) {  // this Gaussian would saturate the pixel: stop before it
+          done = true;
+          wgt = 0.0f;
+          test_T = T;
+        }
+        D += wgt * c.w;
+        T = test_T;
+      }
+    }
+  }
+  if (inside) out[(size_t)py * W + px] = D;
+}
+
 struct GbOut {
   float *means, *scales, *rots, *opac, *colors, *means2d, *conics;
 };
 
+// DEPTH: the accumulator has the tenth sum, dL/d(1/d), which reaches the mean through d (splat_backward_math.h)
+template <bool DEPTH>
 __global__ __launch_bounds__(256) void gs_project_backward_kernel(GbCam cam, const float* __restrict__ means,
                                                                    const float* __restrict__ scales,
                                                                    const float* __restrict__ rots,
                                                                    const float* __restrict__ opac, uint32_t n,
                                                                    const int* __restrict__ radii,
                                                                    const float* __restrict__ acc, GbOut out) {
+  constexpr uint32_t ACC = DEPTH ? GS_BWD_ACC_DEPTH : GS_BWD_ACC;
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
   const bool visible = radii[i] > 0;  // (a culled Gaussian is in no tile's list: its sums are zero)
-  const float* s9 = acc + (size_t)i * GS_BWD_ACC;
+  const float* s9 = acc + (size_t)i * ACC;
   const float dgx = s9[0], dgy = s9[1];
   const float da = -0.5f * GB_L2E * s9[2], db = -GB_L2E * s9[3], dc = -0.5f * GB_L2E * s9[4];
   const float o = opac[i];
@@ -217,7 +332,8 @@ __global__ __launch_bounds__(256) void gs_project_backward_kernel(GbCam cam, con
   }
   float dm[3] = {0.0f, 0.0f, 0.0f}, dsc[3] = {0.0f, 0.0f, 0.0f}, dq[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   if (visible)
-    gs_project_backward_one(cam, means + 3 * i, scales + 3 * i, rots + 4 * i, dgx, dgy, da, db, dc, dm, dsc, dq);
+    gs_project_backward_one<DEPTH>(cam, means + 3 * i, scales + 3 * i, rots + 4 * i, dgx, dgy, da, db, dc, dm, dsc, dq,
+                                   DEPTH ? s9[GS_BWD_ACC] : 0.0f);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     out.means[3 * i + k] = dm[k];
@@ -229,10 +345,11 @@ __global__ __launch_bounds__(256) void gs_project_backward_kernel(GbCam cam, con
 
 hipError_t splat_gaussians_backward(const SplatFrame& f, float* acc, const ptgs_gaussians* g, const float* view,
                                     const float* mvp, float p00, float p11, const float bg[3], const float* dL_dout,
-                                    const ptgs_gaussian_grads* grads, hipStream_t s) {
+                                    const float* dL_dinvdepth, const ptgs_gaussian_grads* grads, hipStream_t s) {
   const uint32_t n = f.n;
+  const bool depth = dL_dinvdepth != nullptr;
   hipError_t e;
-  if ((e = hipMemsetAsync(acc, 0, (size_t)n * GS_BWD_ACC * 4, s))) return e;
+  if ((e = hipMemsetAsync(acc, 0, (size_t)n * (depth ? GS_BWD_ACC_DEPTH : GS_BWD_ACC) * 4, s))) return e;
   GbCam cam;
   for (int k = 0; k < 16; ++k) {
     cam.view[k] = view[k];
@@ -245,13 +362,28 @@ hipError_t splat_gaussians_backward(const SplatFrame& f, float* acc, const ptgs_
   cam.W = f.W;
   cam.H = f.H;
   cam.grid_x = (f.W + GB_TILE - 1) / GB_TILE;
-  hipLaunchKernelGGL(gs_blend_backward_kernel, dim3(f.tiles), dim3(GB_BLOCK), 0, s, f.W, f.H, cam.grid_x, f.ranges,
-                     f.sorted_values, f.rec, bg[0], bg[1], bg[2], (const float4*)dL_dout, acc);
+  if (depth)
+    hipLaunchKernelGGL(gs_blend_backward_kernel<true>, dim3(f.tiles), dim3(GB_BLOCK), 0, s, f.W, f.H, cam.grid_x,
+                       f.ranges, f.sorted_values, f.rec, bg[0], bg[1], bg[2], (const float4*)dL_dout, dL_dinvdepth, acc);
+  else
+    hipLaunchKernelGGL(gs_blend_backward_kernel<false>, dim3(f.tiles), dim3(GB_BLOCK), 0, s, f.W, f.H, cam.grid_x,
+                       f.ranges, f.sorted_values, f.rec, bg[0], bg[1], bg[2], (const float4*)dL_dout,
+                       (const float*)nullptr, acc);
   if ((e = hipGetLastError())) return e;
   const GbOut out = {grads->means, grads->scales, grads->rotations, grads->opacities, grads->colors, grads->means2d,
                      grads->conics};
-  hipLaunchKernelGGL(gs_project_backward_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, cam, g->means, g->scales,
-                     g->rotations, g->opacities, n, f.radii, (const float*)acc, out);
+  if (depth)
+    hipLaunchKernelGGL(gs_project_backward_kernel<true>, dim3((n + 255u) / 256u), dim3(256), 0, s, cam, g->means,
+                       g->scales, g->rotations, g->opacities, n, f.radii, (const float*)acc, out);
+  else
+    hipLaunchKernelGGL(gs_project_backward_kernel<false>, dim3((n + 255u) / 256u), dim3(256), 0, s, cam, g->means,
+                       g->scales, g->rotations, g->opacities, n, f.radii, (const float*)acc, out);
+  return hipGetLastError();
+}
+
+hipError_t splat_gaussians_invdepth(const SplatFrame& f, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(gs_invdepth_kernel, dim3(f.tiles), dim3(GB_BLOCK), 0, s, f.W, f.H, (f.W + GB_TILE - 1) / GB_TILE,
+                     f.ranges, f.sorted_values, f.rec, out);
   return hipGetLastError();
 }
 

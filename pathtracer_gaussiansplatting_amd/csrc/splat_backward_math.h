@@ -18,9 +18,12 @@ struct GbCam {
 // One visible Gaussian: (dL/d means2d (dgx, dgy), dL/d conic (da, db, dc)) -> dL/d mean (dm), the linear
 // scales (dsc) and the un-normalised quaternion (dq), through conic = cov^-1, cov = T Sigma T^T + 0.3 I,
 // T = J W with J at the clamped point, Sigma = R S^2 R^T and q / |q| (gs_preprocess_one's forward, recomputed).
+// DEPTH: dinvd = dL/d(1/d) as well, the inverse depth's share (D = sum wgt / d): it reaches the mean through
+// d = -(V row 2) . (mean, 1) alone, dL/dd = -dinvd / d^2. Order and membership carry no gradient.
+template <bool DEPTH = false>
 PTGS_HD void gs_project_backward_one(const GbCam& cam, const float* mean, const float* scale, const float* rot,
                                      float dgx, float dgy, float da, float db, float dc, float* dm, float* dsc,
-                                     float* dq) {
+                                     float* dq, float dinvd = 0.0f) {
   // ---- the forward again (gs_preprocess_one) ----
   const float* V = cam.view;  // column-major: row r, col c = V[c*4 + r]
   const float* P = cam.mvp;
@@ -128,6 +131,7 @@ PTGS_HD void gs_project_backward_one(const GbCam& cam, const float* mean, const 
   float dd = -(dJ00 * cam.fx + dJ11 * cam.fy) / d2;
   dd -= (clx ? 1.0f : 2.0f) * dJ02 * cam.fx * tx / d3;
   dd -= (cly ? 1.0f : 2.0f) * dJ12 * cam.fy * ty / d3;
+  if (DEPTH) dd -= dinvd / d2;  // ---- 1 / d of the inverse depth ----
   // ---- means2d = ndc2pix(ph.xy / (ph.w + 1e-7)) ----
   const float dnx = dgx * 0.5f * (float)cam.W, dny = dgy * 0.5f * (float)cam.H;
   const float dphx = dnx * pw, dphy = dny * pw, dphw = -(dnx * phx + dny * phy) * pw * pw;

@@ -18,4 +18,10 @@ hipError_t image_loss_l1_dssim(LossWorkspace* ws, const float* image, const floa
                                uint32_t W, uint32_t H, float lambda, float grad_scale, float* loss_out, float* grad,
                                hipStream_t s);
 
+// The L1 on rendered inverse depth against a view-depth target (contract in ptgs.h, arguments checked by the
+// caller); grad may be null. Two kernels on s, no host wait; its per-workgroup sums (16 bytes per 1024 pixels)
+// are a buffer of their own in the workspace, so it does not disturb image_loss_l1_dssim's.
+hipError_t image_loss_invdepth_l1(LossWorkspace* ws, const float* invdepth, const float* target_depth, uint32_t W,
+                                  uint32_t H, float weight, float grad_scale, float* terms, float* grad, hipStream_t s);
+
 }  // namespace ptgs

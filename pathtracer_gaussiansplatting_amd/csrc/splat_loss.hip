@@ -23,6 +23,9 @@
 // three by its registers. Each work-item issues all of its staging loads before the LDS stores.
 // Bytes per pixel: 16 + 4 C read and 36 written by the first kernel, 36 + 16 + 4 C read and 16 written by the
 // second (halo re-reads come from the caches).
+//
+// The depth regulariser (ptgs_image_loss_invdepth_l1) is at the end: an L1 on rendered inverse depth against a
+// view-depth target, one streaming kernel and a final sum of the same kind.
 #include "splat_loss.h"
 
 #include "dev_buf.h"
@@ -303,11 +306,69 @@ static_assert(LS_STEP == LS_WG, "the final sum's step is its workgroup");
 
 bool ls_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
+// The inverse-depth L1 (ptgs_image_loss_invdepth_l1). A workgroup owns LD_PER consecutive pixels, a work-item
+// LD_PER / LS_WG of them, LS_WG apart (coalesced). term = |D - 1.0f / t| in f32 (IEEE divide, no contraction)
+// where t > 0 (+inf included: 1 / t = 0), 0 where t <= 0 or t is NaN; the terms and the supervised count are
+// summed in f64, per work-item in pixel order, then by the fixed tree: one (sum, count) pair per workgroup.
+constexpr uint32_t LD_PER = 4 * LS_WG;
+
+__global__ __launch_bounds__(LS_WG) void gs_loss_invdepth_kernel(const float* __restrict__ invdepth,
+                                                                const float* __restrict__ target, size_t pixels,
+                                                                float k, float* __restrict__ grad,
+                                                                double* __restrict__ partials) {
+  __shared__ double red[2][LS_WG];
+  const uint32_t t = threadIdx.x;
+  double sum = 0.0, count = 0.0;
+  for (uint32_t it = 0; it < LD_PER / LS_WG; ++it) {
+    const size_t p = (size_t)blockIdx.x * LD_PER + it * LS_WG + t;
+    if (p < pixels) {
+      const float tz = target[p];
+      float g = 0.0f;
+      if (tz > 0.0f) {  // (false for NaN)
+        const float diff = invdepth[p] - 1.0f / tz;
+        sum += (double)fabsf(diff);
+        count += 1.0;
+        g = k * loss_sign(diff);
+      }
+      if (grad) grad[p] = g;
+    }
+  }
+  ls_tree_sum(red, sum, count);
+  if (t == 0) {
+    partials[2 * (size_t)blockIdx.x] = sum;
+    partials[2 * (size_t)blockIdx.x + 1] = count;
+  }
+}
+
+__global__ __launch_bounds__(LS_WG) void gs_loss_invdepth_final_kernel(const double* __restrict__ partials,
+                                                                      uint32_t nwg, double pixels, float weight,
+                                                                      float* __restrict__ terms) {
+  __shared__ double red[2][LS_WG];
+  const uint32_t t = threadIdx.x;
+  double sum = 0.0, count = 0.0;
+  for (uint32_t c0 = 0; c0 < nwg; c0 += LS_STEP) {
+    const uint32_t w = c0 + t;
+    if (w < nwg) {
+      sum += partials[2 * (size_t)w];
+      count += partials[2 * (size_t)w + 1];
+    }
+  }
+  ls_tree_sum(red, sum, count);
+  if (t == 0) {
+    const double mean = sum / pixels;
+    terms[0] = (float)((double)weight * mean);
+    terms[1] = (float)mean;
+    terms[2] = (float)count;
+    terms[3] = 0.0f;
+  }
+}
+
 }  // namespace
 
 struct LossWorkspace {
-  DevBuf maps;      // float: LS_MAPS planes of W x H
-  DevBuf partials;  // double: (sum |a - b|, sum m) per workgroup
+  DevBuf maps;            // float: LS_MAPS planes of W x H
+  DevBuf partials;        // double: (sum |a - b|, sum m) per workgroup
+  DevBuf depth_partials;  // double: (sum |D - 1/t|, supervised pixels) per workgroup of the inverse-depth L1
 };
 
 LossWorkspace* loss_workspace_create() { return new LossWorkspace(); }
@@ -354,6 +415,21 @@ hipError_t image_loss_l1_dssim(LossWorkspace* ws, const float* image, const floa
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   gs_loss_final_kernel<<<1, LS_WG, 0, s>>>(partials, nwg, 1.0 / n, lambda, loss_out);
+  return hipGetLastError();
+}
+
+hipError_t image_loss_invdepth_l1(LossWorkspace* ws, const float* invdepth, const float* target_depth, uint32_t W,
+                                  uint32_t H, float weight, float grad_scale, float* terms, float* grad, hipStream_t s) {
+  if (W == 0 || H == 0 || W > LOSS_MAX_SIDE || H > LOSS_MAX_SIDE) return hipErrorInvalidValue;
+  const size_t pixels = (size_t)W * H;
+  const uint32_t nwg = (uint32_t)((pixels + LD_PER - 1) / LD_PER);  // (<= 2^18)
+  hipError_t e;
+  if ((e = ws->depth_partials.ensure(2 * (size_t)nwg * sizeof(double), 0)) != hipSuccess) return e;
+  double* const partials = ws->depth_partials.as<double>();
+  const float k = (float)((double)weight * (double)grad_scale / (double)pixels);
+  gs_loss_invdepth_kernel<<<nwg, LS_WG, 0, s>>>(invdepth, target_depth, pixels, k, grad, partials);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  gs_loss_invdepth_final_kernel<<<1, LS_WG, 0, s>>>(partials, nwg, (double)pixels, weight, terms);
   return hipGetLastError();
 }
 

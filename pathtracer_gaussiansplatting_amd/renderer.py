@@ -265,18 +265,35 @@ class Renderer:
         self._chk(rc, "ptgs_splat_gaussians")
         return st if want_stats else None
 
+    def splat_gaussians_invdepth(self, width: int, height: int, out=None, stream=None):
+        """ptgs_splat_gaussians_invdepth: the expected inverse depth sum(alpha T / d) per pixel of the latest
+        frame (no background term), float32 [H, W] (`out`, or a new device tensor). The frame must be what
+        splat_gaussians_backward accepts (full-frame, published, want_stats=True, this size); it stays valid, so
+        the call can sit between the forward and the backward. Stream-ordered; reproducible (no atomics)."""
+        import torch
+        if out is None:
+            out = torch.empty((height, width), dtype=torch.float32, device=f"cuda:{torch.cuda.current_device()}")
+        self._f32(("out", out, width * height))
+        rc = self.lib.ptgs_splat_gaussians_invdepth(self._h, width, height, _ptr(out), _stream(stream))
+        self._chk(rc, "ptgs_splat_gaussians_invdepth")
+        return out
+
     def splat_gaussians_backward(self, g: dict, ubo: Ubo, width: int, height: int, dL_dout, bg=(0.0, 0.0, 0.0),
-                                 want_means2d: bool = False, want_conics: bool = False, stream=None) -> dict:
+                                 want_means2d: bool = False, want_conics: bool = False, stream=None,
+                                 dL_dinvdepth=None) -> dict:
         """ptgs_splat_gaussians_backward: the gradients of the latest frame, which must be a full-frame
         splat_gaussians(g, ubo, width, height, ..., bg, want_stats=True) of a renderer that publishes
         (FLAG_SPLAT_PUBLISH). dL_dout: float32 [H, W, 4]. Returns new tensors "means", "scales" (linear),
         "rotations" (un-normalised), "opacities", "colors" and, when asked for, "means2d" (dL/d pixel
-        position) and "conics" (dL/d conic a, b, c). Stream-ordered; not bit-reproducible (float atomics)."""
+        position) and "conics" (dL/d conic a, b, c). Stream-ordered; not bit-reproducible (float atomics).
+        dL_dinvdepth: float32 [H, W], the gradient with respect to splat_gaussians_invdepth's output; with it the
+        call is ptgs_splat_gaussians_backward_depth (the gradients of a loss on both, in one pass)."""
         import torch
         n = int(g["means"].shape[0])
         self._f32(("means", g["means"], n * 3), ("scales", g["scales"], n * 3), ("rotations", g["rotations"], n * 4),
                   ("opacities", g["opacities"], n), ("colors", g["colors"], n * 3),
-                  ("dL_dout", dL_dout, width * height * 4))
+                  ("dL_dout", dL_dout, width * height * 4),
+                  *([("dL_dinvdepth", dL_dinvdepth, width * height)] if dL_dinvdepth is not None else []))
         dev = g["means"].device
         shapes = {"means": (n, 3), "scales": (n, 3), "rotations": (n, 4), "opacities": (n,), "colors": (n, 3)}
         if want_means2d:
@@ -288,6 +305,12 @@ class Renderer:
         for k, t in out.items():
             setattr(gr, k, _ptr(t))
         bgc = np.asarray(bg, np.float32)
+        if dL_dinvdepth is not None:
+            rc = self.lib.ptgs_splat_gaussians_backward_depth(self._h, C.byref(_gaussians(g)), C.byref(ubo), width,
+                                                              height, _abi.fptr(bgc), _ptr(dL_dout),
+                                                              _ptr(dL_dinvdepth), C.byref(gr), _stream(stream))
+            self._chk(rc, "ptgs_splat_gaussians_backward_depth")
+            return out
         rc = self.lib.ptgs_splat_gaussians_backward(self._h, C.byref(_gaussians(g)), C.byref(ubo), width, height,
                                                     _abi.fptr(bgc), _ptr(dL_dout), C.byref(gr), _stream(stream))
         self._chk(rc, "ptgs_splat_gaussians_backward")
@@ -446,6 +469,30 @@ class Renderer:
                                                float(grad_scale), _ptr(terms_out), _ptr(grad_out) or None,
                                                _stream(stream))
         self._chk(rc, "ptgs_image_loss_l1_dssim")
+        return terms_out, grad_out
+
+    def invdepth_l1_loss(self, invdepth, target_depth, weight: float = 1.0, grad_out=None, grad_scale: float = 1.0,
+                         terms_out=None, stream=None):
+        """ptgs_image_loss_invdepth_l1: the L1 between a rendered inverse depth [H, W] (splat_gaussians_invdepth)
+        and a VIEW DEPTH target [H, W] (trace_depth's output: +inf where nothing was hit). A pixel is supervised
+        when its target is > 0 (+inf: target inverse depth 0); others (<= 0, NaN) add nothing and get gradient 0.
+        Returns (terms, grad): terms a float32 device tensor [4] = (weight * mean, mean, supervised pixels, 0), the
+        mean over all H W pixels, never read back here; grad is grad_out, float32 [H, W], which receives
+        grad_scale * weight / (H W) * sign(invdepth - 1 / target), or None when grad_out is None. Stream-ordered,
+        no host wait; reproducible (no atomics)."""
+        import torch
+        if invdepth.dim() != 2 or tuple(target_depth.shape) != tuple(invdepth.shape):
+            raise _abi.PtgsError(f"invdepth and target_depth must both be [H, W] (got {tuple(invdepth.shape)}, "
+                                 f"{tuple(target_depth.shape)})")
+        h, w = int(invdepth.shape[0]), int(invdepth.shape[1])
+        if terms_out is None:
+            terms_out = torch.empty(4, dtype=torch.float32, device=invdepth.device)
+        self._f32(("invdepth", invdepth, h * w), ("target_depth", target_depth, h * w), ("terms_out", terms_out, 4),
+                  *([("grad_out", grad_out, h * w)] if grad_out is not None else []))
+        rc = self.lib.ptgs_image_loss_invdepth_l1(self._h, _ptr(invdepth), _ptr(target_depth), w, h, float(weight),
+                                                  float(grad_scale), _ptr(terms_out), _ptr(grad_out) or None,
+                                                  _stream(stream))
+        self._chk(rc, "ptgs_image_loss_invdepth_l1")
         return terms_out, grad_out
 
     # ---------------------------------------------------------------- densification and pruning
