@@ -390,6 +390,22 @@ typedef struct ptgs_scene_build {
     uint32_t deep_stack;    /* 1 when the deep-stack kernel is launched for it */
 } ptgs_scene_build;
 int ptgs_scene_get_build(const ptgs_ctx* ctx, ptgs_scene_build* out);
+/* The path-tracer megakernel walks a compact copy of the resident tree whose topology is its own: for the
+ * two SAH builders' trees it is rebuilt by reinsertion for fewer node steps per ray (hits do not depend on the
+ * tree); PTGS_PT_TREE_OPT=0 / 1 in the environment at upload forces that off / on. ptgs_scene_get_bvh,
+ * ptgs_scene_info and ptgs_scene_build describe the canonical tree either way; this describes the copy. */
+typedef struct ptgs_scene_tree_opt {
+    uint32_t applied;       /* 1: the megakernel walks the optimised copy; 0: the canonical tree's conversion */
+    uint32_t num_nodes;     /* the optimised copy's 4-wide nodes, worst-case stack entries and depth */
+    uint32_t stack_need;    /*   (0 when not applied) */
+    uint32_t depth;
+    uint32_t fan;           /* the fan-out it was collapsed at */
+    uint32_t passes;        /* reinsertion passes run */
+    double area_before;     /* sum of the 4-wide nodes' box areas over the root's: canonical, */
+    double area_after;      /*   and optimised (0 when not applied) */
+    double ms;              /* host time the optimiser took at upload */
+} ptgs_scene_tree_opt;
+int ptgs_scene_get_tree_opt(const ptgs_ctx* ctx, ptgs_scene_tree_opt* out);
 
 /* ---------------- path tracer (raygen_camera.rgen + closesthit/miss/shadow) ---------------- */
 

@@ -221,6 +221,13 @@ class SceneBuild(C.Structure):
                 ("stack_need", C.c_uint32), ("deep_stack", C.c_uint32)]
 
 
+class SceneTreeOpt(C.Structure):
+    """ptgs_scene_tree_opt: the megakernel's traversal copy of the resident tree (reinsertion-optimised or not)."""
+    _fields_ = [("applied", C.c_uint32), ("num_nodes", C.c_uint32), ("stack_need", C.c_uint32), ("depth", C.c_uint32),
+                ("fan", C.c_uint32), ("passes", C.c_uint32), ("area_before", C.c_double), ("area_after", C.c_double),
+                ("ms", C.c_double)]
+
+
 assert C.sizeof(Ubo) == 192 and C.sizeof(RayPush) == 80
 
 # (name, restype, argtypes) of every symbol include/ptgs/*.h declares
@@ -239,6 +246,7 @@ SYMBOLS = {
     "ptgs_scene_get_info": (_I, [_P, C.POINTER(SceneInfo)]),
     "ptgs_scene_get_bvh": (_I, [_P, C.POINTER(BvhBuffers)]),
     "ptgs_scene_get_build": (_I, [_P, C.POINTER(SceneBuild)]),
+    "ptgs_scene_get_tree_opt": (_I, [_P, C.POINTER(SceneTreeOpt)]),
     "ptgs_trace_camera": (_I, [_P, C.POINTER(Ubo), _U, _U, _P, _U, _U, _U, _P]),
     "ptgs_trace_camera_rows": (_I, [_P, C.POINTER(Ubo), _U, _U, _U, _U, _P, _U, _U, _U, _P]),
     "ptgs_trace_torus": (_I, [_P, C.POINTER(Ubo), C.POINTER(RayPush), _P, _U, _P, _P]),

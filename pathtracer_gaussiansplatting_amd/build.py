@@ -20,10 +20,10 @@ INCLUDE = os.path.join(ROOT, "include")
 BUILD = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libptgs.so")
 
-SOURCES = ["api.cpp", "bvh.cpp", "bvh_gpu.hip", "bvh_sah_gpu.hip", "bvh_collapse_gpu.hip", "capture.cpp", "capture_io.cpp", "comm.cpp", "jpeg.cpp", "scene.cpp", "textures.cpp",
+SOURCES = ["api.cpp", "bvh.cpp", "bvh_opt.cpp", "bvh_gpu.hip", "bvh_sah_gpu.hip", "bvh_collapse_gpu.hip", "capture.cpp", "capture_io.cpp", "comm.cpp", "jpeg.cpp", "scene.cpp", "textures.cpp",
            "pt_kernels.hip", "pt_wavefront.hip", "raster.hip", "splat.hip", "splat_backward.hip", "splat_sh.hip", "splat_densify.hip", "splat_loss.hip", "splat_adam.hip", "knn.hip", "gltf.cpp", "image_decode.cpp", "ply.cpp", "sampling.cpp"]
-# pure host code (scene ingest): plain g++, no device pass
-HOST_SOURCES = {"gltf.cpp", "image_decode.cpp", "ply.cpp", "sampling.cpp", "capture_io.cpp", "jpeg.cpp"}
+# pure host code (scene ingest, the traversal tree's optimiser): plain g++, no device pass
+HOST_SOURCES = {"bvh_opt.cpp", "gltf.cpp", "image_decode.cpp", "ply.cpp", "sampling.cpp", "capture_io.cpp", "jpeg.cpp"}
 # per-source extra flags. pt_kernels.hip: SimplifyCFG's common-store sinking merges stores to
 # different Payload fields from the branches of closest_hit into one store through a phi of
 # addresses, which SROA cannot split: the payload then stays a private (scratch) object.

@@ -26,6 +26,7 @@
 #include "../../include/ptgs/ptgs.h"
 #include "bvh.h"
 #include "bvh_gpu.h"
+#include "bvh_opt.h"
 #include "bvh_tries.h"
 #include "knn.h"
 #include "hostmath.h"
@@ -57,6 +58,7 @@ struct ptgs_ctx {
   std::vector<void*> scene_allocs;
   ptgs_scene_info info{};
   ptgs_scene_build build{};  // which builder's tree is resident (ptgs_scene_get_build)
+  ptgs_scene_tree_opt tree_opt{};  // the megakernel's traversal copy of it (ptgs_scene_get_tree_opt)
   unsigned long long* counters = nullptr;  // 8 x u64
   SplatFrames frames;  // the splat frame calls' workspaces, streams, events, run and pending reports
   DensifyWorkspace* densify = nullptr;  // the densification plan (ptgs_gaussians_densify_plan / _apply)
@@ -313,6 +315,10 @@ int check_node_window(ptgs_ctx* c) {
 // are re-encoded into the fewest bits this tree needs, so that a stack entry of the closest-hit walk
 // carries the child's entry distance in the bits left (bvh.h stack_layout, stack_key.h).
 // PTGS_PT_STACK_KEY_BITS forces the key's width (tests: 0 = never cull).
+// The copy's topology is its own: the trees of the two SAH builders (the same canonical tree) are rebuilt by
+// reinsertion for fewer node steps per ray (bvh_opt.h), held to the stack bound the canonical tree's kernel
+// instantiation assumes; the LBVH, whose point is rebuild time, is converted as it is. PTGS_PT_TREE_OPT=0 / 1
+// forces it off / on. The canonical nodes, scene_info and scene_build describe the canonical tree either way.
 int upload_traversal_nodes(ptgs_ctx* c, std::vector<float>& host_n4, DevScene& s) {
   const size_t nf = (size_t)c->info.num_bvh_nodes * 32;
   if (host_n4.size() != nf) {
@@ -321,16 +327,28 @@ int upload_traversal_nodes(ptgs_ctx* c, std::vector<float>& host_n4, DevScene& s
   }
   int force = -1;
   if (const char* e = getenv("PTGS_PT_STACK_KEY_BITS")) force = std::max(0, atoi(e));
+  bool optimise = c->build.builder != PTGS_BUILDER_GPU_LBVH;
+  if (const char* e = getenv("PTGS_PT_TREE_OPT")) optimise = atoi(e) != 0;
   std::vector<uint32_t> n64;
   StackLayout sl;
-  if (!make_traversal_nodes(host_n4.data(), c->info.num_bvh_nodes, force, n64, sl))
+  TreeOptInfo oi;
+  if (!make_opt_traversal_nodes(host_n4.data(), c->info.num_bvh_nodes, (int)c->build.fan,
+                                s.deep_stack ? PTGS_STACK_TOTAL : PTGS_STACK, optimise, force, n64, sl, oi))
     return fail(c, PTGS_ERANGE, "BVH node extents beyond the compact nodes' step range (2^-100 .. 2^100)");
+  c->tree_opt = ptgs_scene_tree_opt{oi.applied, oi.num_nodes, oi.need, oi.depth, oi.fan, oi.passes,
+                                    oi.area_before, oi.area_after, oi.ms};
   s.stk_key_mask = sl.key_mask;
   s.leaf_shift = sl.leaf_shift;
   s.leaf_start_mask = sl.leaf_start_mask;
-  if (getenv("PTGS_BVH_LOG"))
+  if (getenv("PTGS_BVH_LOG")) {
+    if (optimise)
+      fprintf(stderr, "[ptgs] traversal tree: %s in %.1f ms (%u passes): nodes %u -> %u, stack need %u -> %u, depth %u -> %u, "
+              "fan %u, area sum %.3f -> %.3f\n", oi.applied ? "optimised" : "not applied", oi.ms, oi.passes,
+              c->info.num_bvh_nodes, oi.num_nodes, c->build.stack_need, oi.need, c->info.bvh_depth, oi.depth, oi.fan,
+              oi.area_before, oi.area_after);
     fprintf(stderr, "[ptgs] stack word:%u link bits, %u key bits (mask %08x), leaf shift %u\n", sl.ref_bits, sl.key_bits,
             sl.key_mask, sl.leaf_shift);
+  }
   return upload(c, (const uint4*)n64.data(), n64.size() / 4, &s.nodes64);
 }
 
@@ -514,6 +532,7 @@ int ptgs_scene_upload(ptgs_ctx* c, const ptgs_scene_desc* d) {
   free_scene(c);
   c->info = ptgs_scene_info{};
   c->build = ptgs_scene_build{};
+  c->tree_opt = ptgs_scene_tree_opt{};
   DevScene s{};
   // BVH: the host binned-SAH build (default), or with PTGS_FLAG_GPU_BVH one of the GPU builders (the SAH
   // build with the host's tries, or with PTGS_FLAG_GPU_LBVH the LBVH), falling back to the host build when
@@ -546,6 +565,13 @@ int ptgs_scene_get_build(const ptgs_ctx* c, ptgs_scene_build* out) {
   if (!c || !out) return PTGS_EINVAL;
   if (!c->has_scene) return PTGS_ENOSCENE;
   *out = c->build;
+  return PTGS_OK;
+}
+
+int ptgs_scene_get_tree_opt(const ptgs_ctx* c, ptgs_scene_tree_opt* out) {
+  if (!c || !out) return PTGS_EINVAL;
+  if (!c->has_scene) return PTGS_ENOSCENE;
+  *out = c->tree_opt;
   return PTGS_OK;
 }
 

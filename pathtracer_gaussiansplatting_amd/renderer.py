@@ -16,8 +16,8 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (BvhBuffers, Gaussians, RayPush, SceneBuild, SceneInfo, SplatBuffers, SplatStats, SplatStatus,
-                   TraceStats, Ubo)
+from ._abi import (BvhBuffers, Gaussians, RayPush, SceneBuild, SceneInfo, SceneTreeOpt, SplatBuffers, SplatStats,
+                   SplatStatus, TraceStats, Ubo)
 
 
 def _ptr(x) -> int:
@@ -113,6 +113,13 @@ class Renderer:
         b = SceneBuild()
         self._chk(self.lib.ptgs_scene_get_build(self._h, C.byref(b)), "ptgs_scene_get_build")
         return b
+
+    def scene_tree_opt(self) -> SceneTreeOpt:
+        """The megakernel's traversal copy of the resident tree: reinsertion-optimised (applied = 1) or the
+        canonical tree's conversion, with its node count, stack need, depth, area sums and host time."""
+        t = SceneTreeOpt()
+        self._chk(self.lib.ptgs_scene_get_tree_opt(self._h, C.byref(t)), "ptgs_scene_get_tree_opt")
+        return t
 
     # ---------------------------------------------------------------- path tracer
     def trace_camera(self, ubo: Ubo, width: int, height: int, accum, spp: int = 1, frame_stride: int = 1,
