@@ -35,7 +35,8 @@ def view_depth(means, view, dtype):
 def evaluate(g, ubo, W, H, bg, frame, dL_dout, dL_dinv, dtype=torch.float64):
     """g: dict of numpy arrays; frame: oracle.splat_gaussians(g, ubo, W, H, bg); dL_dout [H, W, 4], dL_dinv [H, W].
     Returns {"image" [H, W, 4], "invdepth" [H, W], "grads" / "grads_color" / "grads_depth" {GRAD_KEYS + "invd":
-    numpy float64}, "borderline", "clamped", "stopped", "empty" [H, W] bool: the pixels of tiles without a list}.
+    numpy float64}, "borderline", "border_pixels" [H, W] bool (as splat_grad_ref.evaluate counts them), "clamped",
+    "stopped", "empty" [H, W] bool: the pixels of tiles without a list}.
     "invd" is dL/d(1 / d) per Gaussian, the tenth sum of the blend backward."""
     n = g["means"].shape[0]
     leaf = {k: torch.tensor(np.asarray(g[k], np.float64), dtype=dtype, requires_grad=True)
@@ -58,6 +59,7 @@ def evaluate(g, ubo, W, H, bg, frame, dL_dout, dL_dinv, dtype=torch.float64):
     loss_c = torch.zeros((), dtype=dtype)
     loss_d = torch.zeros((), dtype=dtype)
     borderline = clamped_n = stopped_n = 0
+    border_pixels = np.zeros((H, W), bool)
     for t in range(gx_t * gy_t):
         ty_, tx_ = divmod(t, gx_t)
         ys = torch.arange(ty_ * TILE, min(H, (ty_ + 1) * TILE))
@@ -90,9 +92,11 @@ def evaluate(g, ubo, W, H, bg, frame, dL_dout, dL_dinv, dtype=torch.float64):
             pos = torch.arange(len(ids))[None, :]
             active = pos < first[:, None]
             seen = pos <= first[:, None]  # evaluated entries (the stopping one included)
-            borderline += int((seen & ((ed * 255.0 - 1.0).abs() < R.BORDER)).sum())
-            borderline += int((seen & ((ed / 0.99 - 1.0).abs() < R.BORDER)).sum())
-            borderline += int((seen & ((keep / 1e-4 - 1.0).abs() < R.BORDER)).any(1).sum())
+            near_skip = seen & ((ed * 255.0 - 1.0).abs() < R.BORDER)
+            near_clamp = seen & ((ed / 0.99 - 1.0).abs() < R.BORDER)
+            near_stop = (seen & ((keep / 1e-4 - 1.0).abs() < R.BORDER)).any(1)
+            borderline += int(near_skip.sum()) + int(near_clamp.sum()) + int(near_stop.sum())
+            border_pixels[py.numpy(), px.numpy()] = (near_skip.any(1) | near_clamp.any(1) | near_stop).numpy()
             clamped_n += int((active & clamp & ~skip).sum())
             stopped_n += int(stop.any(1).sum())
             alpha = alpha * active.to(dtype)
@@ -124,7 +128,7 @@ def evaluate(g, ubo, W, H, bg, frame, dL_dout, dL_dinv, dtype=torch.float64):
 
     return {"image": image.double().numpy(), "invdepth": depth.double().numpy(), "empty": empty,
             "grads": grads_of(loss_c + loss_d), "grads_color": grads_of(loss_c), "grads_depth": grads_of(loss_d),
-            "borderline": borderline, "clamped": clamped_n, "stopped": stopped_n}
+            "borderline": borderline, "border_pixels": border_pixels, "clamped": clamped_n, "stopped": stopped_n}
 
 
 def make_dinv(name, W, H):
@@ -146,6 +150,26 @@ def case_reference(name, oracle):
             c[key] = evaluate(c["g"], c["ubo"], c["W"], c["H"], c["bg"], c["frame"], c["dL"], c["dinv"], dt)
         _CACHE[name] = c
     return _CACHE[name]
+
+
+_FRAME_DINV_SEED = {k: v + 500 for k, v in R._FRAME_DL_SEED.items()}
+_FRAME_CACHE = {}
+
+
+def frame_case_reference(name, oracle):
+    """case_reference() for a splat_grad_ref.FRAME_CASES entry. "dL" is splat_grad_ref's masked one and "dinv" is
+    exactly 0 on the same "mask" (the border_pixels of splat_grad_ref's first float64 evaluation; this module's
+    evaluate() takes the same decisions, tests/test_splat_depth_ref.py compares the two masks)."""
+    if name not in _FRAME_CACHE:
+        base = R.frame_case_reference(name, oracle)
+        c = {k: base[k] for k in ("name", "g", "ubo", "W", "H", "bg", "dL", "frame", "mask")}
+        rng = np.random.default_rng(_FRAME_DINV_SEED[name])
+        c["dinv"] = (rng.normal(size=(c["H"], c["W"])) * DINV_SCALE).astype(np.float32)
+        c["dinv"][c["mask"]] = 0.0
+        for key, dt in (("r64", torch.float64), ("r32", torch.float32)):
+            c[key] = evaluate(c["g"], c["ubo"], c["W"], c["H"], c["bg"], c["frame"], c["dL"], c["dinv"], dt)
+        _FRAME_CACHE[name] = c
+    return _FRAME_CACHE[name]
 
 
 def part(c, which):

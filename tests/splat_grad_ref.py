@@ -8,7 +8,8 @@ T < 1e-4 stop, the 0.99 clamp) are taken from a detached evaluation and applied 
 gives the gradients. evaluate() also counts the borderline decisions, so that the tests can insist on
 cases without any (a decision within 1e-3 relative of its threshold could fall either way in float32).
 
-The cases of tests/test_splat_grad_ref.py (CPU) and tests/test_splat_backward_gpu.py (GPU) are built here.
+The cases of tests/test_splat_grad_ref.py (CPU) and tests/test_splat_backward_gpu.py (GPU) are built here, and the
+training-size FRAME_CASES of tests/test_splat_backward_frames_gpu.py, whose borderline pixels take no part.
 """
 import numpy as np
 import torch
@@ -68,9 +69,10 @@ def _project(means, scales, rots, view, proj, W, H):
 
 def evaluate(g, ubo, W, H, bg, frame, dL_dout, dtype=torch.float64):
     """g: dict of float32 numpy arrays; frame: oracle.splat_gaussians(g, ubo, W, H, bg); dL_dout [H, W, 4].
-    Returns {"image" [H, W, 4], "grads" {GRAD_KEYS: numpy float64}, "borderline", "clamped", "stopped", "tiles"}:
-    borderline = pairs whose o exp(power) lies within 1e-3 relative of 1/255 or of 0.99 + pixels whose stop
-    test lies within 1e-3 relative of 1e-4; clamped = pairs blended at 0.99; stopped = pixels that stop
+    Returns {"image" [H, W, 4], "grads" {GRAD_KEYS: numpy float64}, "borderline", "border_pixels", "clamped",
+    "stopped", "tiles"}: borderline = pairs whose o exp(power) lies within 1e-3 relative of 1/255 or of 0.99 +
+    pixels whose stop test lies within 1e-3 relative of 1e-4; border_pixels = bool [H, W], the pixels with any
+    of these among their evaluated entries; clamped = pairs blended at 0.99; stopped = pixels that stop
     on T < 1e-4; tiles = per tile {"n": the list's length, "first": per pixel inside the image the position of
     the entry that stops it (n: none), "quads": per entry the 8x8 quadrants (bit (x >= 8) + 2 (y >= 8)) holding a
     pixel that evaluates it with alpha >= 1/255}."""
@@ -82,8 +84,9 @@ def evaluate(g, ubo, W, H, bg, frame, dL_dout, dtype=torch.float64):
     slot[vis] = np.arange(len(vis))
     vt = torch.from_numpy(vis)
     m2d, conic = _project(leaf["means"][vt], leaf["scales"][vt], leaf["rotations"][vt], ubo.view, ubo.proj, W, H)
-    m2d.retain_grad()
-    conic.retain_grad()
+    if m2d.requires_grad:  # (not under torch.no_grad(): a run for the image and the counts alone)
+        m2d.retain_grad()
+        conic.retain_grad()
     opac, cols = leaf["opacities"][vt], leaf["colors"][vt]
     bgt = torch.tensor(np.asarray(bg, np.float64), dtype=dtype)
     go = torch.tensor(np.asarray(dL_dout, np.float64), dtype=dtype)
@@ -92,6 +95,7 @@ def evaluate(g, ubo, W, H, bg, frame, dL_dout, dtype=torch.float64):
     image = torch.zeros((H, W, 4), dtype=dtype)
     loss = torch.zeros((), dtype=dtype)
     borderline = clamped_n = stopped_n = 0
+    border_pixels = np.zeros((H, W), bool)
     tiles = []
     for t in range(gx_t * gy_t):
         ty_, tx_ = divmod(t, gx_t)
@@ -124,9 +128,11 @@ def evaluate(g, ubo, W, H, bg, frame, dL_dout, dtype=torch.float64):
             pos = torch.arange(len(ids))[None, :]
             active = pos < first[:, None]
             seen = pos <= first[:, None]  # evaluated entries (the stopping one included)
-            borderline += int((seen & ((ed * 255.0 - 1.0).abs() < BORDER)).sum())
-            borderline += int((seen & ((ed / 0.99 - 1.0).abs() < BORDER)).sum())
-            borderline += int((seen & ((keep / 1e-4 - 1.0).abs() < BORDER)).any(1).sum())
+            near_skip = seen & ((ed * 255.0 - 1.0).abs() < BORDER)
+            near_clamp = seen & ((ed / 0.99 - 1.0).abs() < BORDER)
+            near_stop = (seen & ((keep / 1e-4 - 1.0).abs() < BORDER)).any(1)
+            borderline += int(near_skip.sum()) + int(near_clamp.sum()) + int(near_stop.sum())
+            border_pixels[py.numpy(), px.numpy()] = (near_skip.any(1) | near_clamp.any(1) | near_stop).numpy()
             clamped_n += int((active & clamp & ~skip).sum())
             stopped_n += int(stop.any(1).sum())
             tiles[t]["first"] = first.numpy().copy()
@@ -155,8 +161,8 @@ def evaluate(g, ubo, W, H, bg, frame, dL_dout, dtype=torch.float64):
         if m2d.grad is not None:
             grads["means2d"][vis] = m2d.grad.double().numpy()
             grads["conics"][vis] = conic.grad.double().numpy()
-    return {"image": image.double().numpy(), "grads": grads, "borderline": borderline, "clamped": clamped_n,
-            "stopped": stopped_n, "tiles": tiles}
+    return {"image": image.double().numpy(), "grads": grads, "borderline": borderline,
+            "border_pixels": border_pixels, "clamped": clamped_n, "stopped": stopped_n, "tiles": tiles}
 
 
 def rel_l2(a, b):
@@ -338,6 +344,104 @@ def make_case(name, **kw):
     return g, make_ubo(W, H, *(pose[0] if pose else ())), W, H, BG, dL
 
 
+# ---------------------------------------------------------------------------------------------------------
+# frame cases: training-size frames (tens of thousands of pairs, lists of several staged batches, tile indices
+# beyond 64). At that size some evaluated alpha always lies within BORDER of a threshold, so these cases do not
+# insist on zero borderline decisions: frame_case_reference() sets the upstream gradient to exactly 0 at the
+# pixels where the float64 reference counts one (evaluate()'s "border_pixels"). A pixel with a zero upstream
+# gradient contributes exactly nothing to any gradient, whichever way its decisions fall, so the comparison on
+# all other pixels needs no allowance for decisions. They are kept apart from CASES, whose tests assert
+# borderline == 0.
+# ---------------------------------------------------------------------------------------------------------
+def tile_order(g, W, H, pose=()):
+    """The Gaussians reordered by the 16x16 tile of their 2D mean (projected in float64, clipped to the grid),
+    row-major and stable: the order a trainer gives its parameters to stay on the fused front end (the backward
+    refuses `ids`, so the spatial order is the caller's)."""
+    view, proj = _view_proj(W, H, pose)
+    ph = np.c_[np.asarray(g["means"], np.float64), np.ones(len(g["means"]))] @ (proj @ view).T
+    pw = 1.0 / (ph[:, 3] + 1e-7)
+    mx, my = ((ph[:, 0] * pw + 1.0) * W - 1.0) * 0.5, ((ph[:, 1] * pw + 1.0) * H - 1.0) * 0.5
+    gx, gy = (W + TILE - 1) // TILE, (H + TILE - 1) // TILE
+    tx = np.clip(np.floor(mx / TILE), 0, gx - 1).astype(np.int64)
+    ty = np.clip(np.floor(my / TILE), 0, gy - 1).astype(np.int64)
+    order = np.argsort(ty * gx + tx, kind="stable")
+    return {k: np.asarray(v)[order] for k, v in g.items()}
+
+
+def _frame_field(seed=9):
+    """320x180, 20x12 tiles with a partial bottom row: 20000 Gaussians, tens of thousands of pairs, dozens of lists
+    above 256 and above 512 pairs, 79 workgroups of the projection backward."""
+    W, H = 320, 180
+    return tile_order(Y.gaussians_c2(20000, seed=seed), W, H), W, H
+
+
+def _frame_layers(seed=9):
+    """208x120: scales x3 and every third opacity exactly 1.0: pixels that stop and pairs blended at 0.99 in
+    quantity, all over the image."""
+    W, H = 208, 120
+    g = Y.gaussians_c2(8000, seed=seed)
+    g["scales"] = g["scales"] * np.float32(3.0)
+    g["opacities"][::3] = 1.0
+    return tile_order(g, W, H), W, H
+
+
+def _frame_crowd(seed=9):
+    """160x96: the field's Gaussians on a quarter of its pixels: lists above 2048 pairs (more than eight staged
+    batches), above the fused rows' capacity."""
+    W, H = 160, 96
+    return tile_order(Y.gaussians_c2(20000, seed=seed), W, H), W, H
+
+
+# (tile x, tile y): Gaussians placed there. wide: 125 x 3 tiles (the last column and the last row partial);
+# tall: 3 x 69 tiles (likewise). The partial tiles' means lie inside the image (box).
+WIDE_TILES = {(0, 0): 40, (63, 1): 70, (64, 1): 130, (123, 0): 300, (124, 2): 60}
+TALL_TILES = {(0, 0): 40, (1, 33): 70, (2, 67): 280, (1, 68): 300}
+
+
+def _frame_placed(W, H, placed, seed):
+    view, proj = _view_proj(W, H, POSE)
+    rng = np.random.default_rng(seed)
+    parts = []
+    for (tx, ty), n in placed.items():
+        partial = 16 * (tx + 1) > W or 16 * (ty + 1) > H
+        parts.append(_small_in_tile(rng, n, tx, ty, W, H, view, proj, (0.05, 0.35),
+                                    box=(1.5, 6.5) if partial else (4.5, 10.5)))
+    return _concat(parts), W, H, POSE
+
+
+def _frame_wide(seed=31):
+    """1992x40 at POSE: pixel x up to 1991 (float32 resolves 1.2e-4 there), grid_x = 125."""
+    return _frame_placed(1992, 40, WIDE_TILES, 9000 + seed)
+
+
+def _frame_tall(seed=32):
+    """40x1096 at POSE: pixel y up to 1095, grid_y = 69 with grid_x = 3."""
+    return _frame_placed(40, 1096, TALL_TILES, 9000 + seed)
+
+
+FRAME_CASES = {"field": _frame_field, "layers": _frame_layers, "crowd": _frame_crowd, "wide": _frame_wide,
+               "tall": _frame_tall}
+_FRAME_DL_SEED = {"field": 1100, "layers": 1101, "crowd": 1102, "wide": 1103, "tall": 1104}
+MASK_CAP = 0.01  # at most this share of a frame case's pixels may be masked (a cap, not a measurement)
+
+
+def make_frame_case(name):
+    """(g, ubo, W, H, bg, dL_dout) of a FRAME_CASES entry, dL_dout not yet masked."""
+    g, W, H, *pose = FRAME_CASES[name]()
+    g = {k: np.ascontiguousarray(v, np.float32) for k, v in g.items()}
+    rng = np.random.default_rng(_FRAME_DL_SEED[name])
+    dL = rng.normal(size=(H, W, 4)).astype(np.float32)
+    return g, make_ubo(W, H, *(pose[0] if pose else ())), W, H, BG, dL
+
+
+def touched_runs(frame, W, H):
+    """The (256-Gaussian chunk, tile) runs the frame's pairs touch, as the front ends count them."""
+    ranges = np.asarray(frame["ranges"]).reshape(-1, 2).astype(np.int64)
+    tile = np.repeat(np.arange(len(ranges)), ranges[:, 1] - ranges[:, 0])
+    vals = np.concatenate([np.asarray(frame["vals"][a:b], np.int64) for a, b in ranges]) if len(ranges) else tile
+    return len(np.unique(tile * (1 << 32) + vals // 256))
+
+
 def ewa_clamped(g, ubo, frame):
     """(in x, in y): per Gaussian, visible in the oracle frame and beyond the EWA clamp (|pv.x / d| > 1.3 / P00,
     |pv.y / d| > 1.3 / |P11|), computed in float64 from the ubo."""
@@ -394,3 +498,23 @@ def case_reference(name, oracle):
         r32 = evaluate(g, ubo, W, H, bg, frame, dL, torch.float32)
         _CACHE[name] = {"name": name, "g": g, "ubo": ubo, "W": W, "H": H, "bg": bg, "dL": dL, "frame": frame, "r64": r64, "r32": r32}
     return _CACHE[name]
+
+
+_FRAME_CACHE = {}
+
+
+def frame_case_reference(name, oracle):
+    """case_reference() for a FRAME_CASES entry, plus "mask": the border_pixels of a first float64 evaluation.
+    "dL" is exactly 0 there, and "r64" / "r32" are computed with that masked gradient. The mask comes from the
+    float64 reference alone."""
+    if name not in _FRAME_CACHE:
+        g, ubo, W, H, bg, dL = make_frame_case(name)
+        frame = oracle.splat_gaussians(g, ubo, W, H, bg=bg)
+        with torch.no_grad():
+            mask = evaluate(g, ubo, W, H, bg, frame, dL, torch.float64)["border_pixels"]
+        dL[mask] = 0.0
+        r64 = evaluate(g, ubo, W, H, bg, frame, dL, torch.float64)
+        r32 = evaluate(g, ubo, W, H, bg, frame, dL, torch.float32)
+        _FRAME_CACHE[name] = {"name": name, "g": g, "ubo": ubo, "W": W, "H": H, "bg": bg, "dL": dL, "frame": frame,
+                              "mask": mask, "r64": r64, "r32": r32}
+    return _FRAME_CACHE[name]

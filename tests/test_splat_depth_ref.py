@@ -124,6 +124,10 @@ def test_projection_backward_depth_on_the_host(case, project_backward_depth_bin,
     """gs_project_backward_one<true> on the host, fed the reference's dL/d(means2d, conic, 1/d): dL/d(means, scales,
     rotations) within max(1e-4, 8 e32) of the reference on the whole array and on each subset, for the full
     gradients and for the depth part alone."""
+    _host_projection_backward_depth(case, project_backward_depth_bin, tmp_path, which)
+
+
+def _host_projection_backward_depth(case, project_backward_depth_bin, tmp_path, which):
     g, W, H, u = case["g"], case["W"], case["H"], case["ubo"]
     view, proj = np.array(u.view, np.float32), np.array(u.proj, np.float32)
     mvp = (proj.reshape(4, 4).T @ view.reshape(4, 4).T).T.reshape(-1).astype(np.float32)
@@ -147,6 +151,65 @@ def test_projection_backward_depth_on_the_host(case, project_backward_depth_bin,
         full[vis] = out[:, sl]
         failed += R.check_bounds(c, k, full, f"host projection backward, {which}")
     assert not failed, failed
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the frame cases (splat_grad_ref.FRAME_CASES): both upstream gradients are exactly 0 on the borderline pixels
+# ---------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module", params=sorted(R.FRAME_CASES))
+def frame_case(request, oracle_lib):
+    return Z.frame_case_reference(request.param, oracle_lib)
+
+
+def test_frame_case_mask(frame_case):
+    """This module's evaluate() marks the pixels splat_grad_ref masked; dL and dinv are exactly 0 there and
+    nowhere else; the share is at most 1%; no borderline decision is left on a pixel with a non-zero gradient."""
+    c = frame_case
+    base = R.frame_case_reference(c["name"], None)  # (cached by the fixture)
+    assert np.array_equal(c["r64"]["border_pixels"], c["mask"]) and np.array_equal(c["mask"], base["mask"])
+    assert float(c["mask"].mean()) <= R.MASK_CAP
+    assert not np.any(c["dL"][c["mask"]]) and not np.any(c["dinv"][c["mask"]])
+    live = np.any(c["dL"] != 0.0, -1) | (c["dinv"] != 0.0)
+    assert np.array_equal(live, ~c["mask"]) and not np.any(c["r64"]["border_pixels"] & live)
+    assert c["r64"]["borderline"] == base["r64"]["borderline"]
+    assert c["r64"]["clamped"] == base["r64"]["clamped"] and c["r64"]["stopped"] == base["r64"]["stopped"]
+
+
+def test_frame_reference_maps(frame_case):
+    """Outside the mask the colour image is the oracle's (< 1e-4) and splat_grad_ref's; D is non-zero; the
+    colour-only gradients are splat_grad_ref's and the depth-only ones are not hidden by them."""
+    c = frame_case
+    base = R.frame_case_reference(c["name"], None)
+    keep = ~c["mask"]
+    err = R.rel_l2(c["r64"]["image"][keep], c["frame"]["image"][keep])
+    print(f"{c['name']}: float64 reference vs oracle image outside the mask rel L2 {err:.2e}")
+    assert err < 1e-4 and np.abs(c["r64"]["image"] - base["r64"]["image"]).max() < 1e-12
+    assert c["r64"]["invdepth"].max() > 0.05 and not np.any(c["r64"]["invdepth"][c["r64"]["empty"]])
+    gc, gd = c["r64"]["grads_color"], c["r64"]["grads_depth"]
+    ratio = np.linalg.norm(gd["means"]) / np.linalg.norm(gc["means"])
+    print(f"{c['name']}: |d means| depth / colour {ratio:.3f}")
+    assert 0.1 < ratio < 10.0
+    for k in R.GRAD_KEYS:
+        assert R.rel_l2(gc[k], base["r64"]["grads"][k]) < 1e-12, k
+        assert R.rel_l2(gc[k] + gd[k], c["r64"]["grads"][k]) < 1e-12, k
+
+
+def test_frame_float32_reference_error(frame_case):
+    """e32 of the full and of the depth-only gradients, per key: printed (the GPU bound follows it)."""
+    for which in ("grads", "grads_depth"):
+        for k in R.GRAD_KEYS:
+            if which == "grads_depth" and k == "colors":
+                continue
+            ref = frame_case["r64"][which][k]
+            assert np.isfinite(ref).all() and np.linalg.norm(ref) > 0
+            assert np.isfinite(frame_case["r32"][which][k]).all()
+            print(f"{frame_case['name']} {which} {k}: e32 {R.rel_l2(frame_case['r32'][which][k], ref):.2e}")
+
+
+@pytest.mark.parametrize("which", ["grads", "grads_depth"])
+def test_projection_backward_depth_on_the_host_frames(frame_case, project_backward_depth_bin, tmp_path, which):
+    """test_projection_backward_depth_on_the_host on the frame cases."""
+    _host_projection_backward_depth(frame_case, project_backward_depth_bin, tmp_path, which)
 
 
 def test_depth_entry_points_are_exported(native_lib):

@@ -1,7 +1,8 @@
 """The backward pass's reference (tests/splat_grad_ref.py) and its cases, checked without a GPU: the float64
 evaluation reproduces the oracle's image, every case has the structure the GPU tests rely on and no borderline
 decision, the per-Gaussian projection backward built for the host matches the reference, and the native library
-exports the backward entry point."""
+exports the backward entry point. The frame cases (FRAME_CASES) are checked likewise, with their mask in the place
+of the zero count."""
 import os
 import struct
 import subprocess
@@ -132,6 +133,10 @@ def test_projection_backward_on_the_host(case, project_backward_bin, tmp_path):
     reference's dL/d(means2d, conic): dL/d(means, scales, rotations) within max(1e-4, 8 e32) of the reference, per
     array and on each of splat_grad_ref.subsets (the quarters by gradient norm, the Gaussians beyond the EWA clamp),
     e32 taken on the same rows."""
+    _host_projection_backward(case, project_backward_bin, tmp_path)
+
+
+def _host_projection_backward(case, project_backward_bin, tmp_path):
     g, W, H, u = case["g"], case["W"], case["H"], case["ubo"]
     view, proj = np.array(u.view, np.float32), np.array(u.proj, np.float32)
     mvp = (proj.reshape(4, 4).T @ view.reshape(4, 4).T).T.reshape(-1).astype(np.float32)
@@ -154,6 +159,101 @@ def test_projection_backward_on_the_host(case, project_backward_bin, tmp_path):
         full[vis] = out[:, sl]
         failed += R.check_bounds(case, k, full, "host projection backward")  # the whole array and every subset
     assert not failed, failed
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the frame cases (splat_grad_ref.FRAME_CASES): training-size frames whose borderline pixels take no part
+# ---------------------------------------------------------------------------------------------------------
+GS_MID, GS_FUSED_MAX_SCAP, GS_FUSED_RUNS_PER_TILE = 512, 2048, 32  # csrc/splat_plan.h
+
+
+@pytest.fixture(scope="module", params=sorted(R.FRAME_CASES))
+def frame_case(request, oracle_lib):
+    return R.frame_case_reference(request.param, oracle_lib)
+
+
+def test_frame_case_structure(frame_case):
+    """What the GPU tests rely on, from the oracle's frame: the list lengths that decide the front end and the
+    sorts, the tile grid's extent, the pixels that stop and the pairs blended at 0.99."""
+    c, name = frame_case, frame_case["name"]
+    f, W, H = c["frame"], c["W"], c["H"]
+    gx, gy = (W + 15) // 16, (H + 15) // 16
+    grid = _counts(c).reshape(gy, gx)
+    n, largest = len(c["g"]["means"]), int(grid.max())
+    per_tile = R.touched_runs(f, W, H) / (gx * gy)
+    print(f"{name}: {W}x{H}, {gx}x{gy} tiles, n {n}, K {f['K']}, longest list {largest}, lists above 256 / {GS_MID} / "
+          f"1024: {(grid > 256).sum()} / {(grid > GS_MID).sum()} / {(grid > 1024).sum()}, touched runs per tile "
+          f"{per_tile:.2f}, stopped {c['r64']['stopped']}, clamped {c['r64']['clamped']}, "
+          f"projection workgroups {(n + 255) // 256}")
+    assert f["K"] == int(grid.sum()) and any(v != 0.0 for v in c["bg"])
+    assert per_tile <= GS_FUSED_RUNS_PER_TILE  # the policy asks for the fused front end
+    if name == "crowd":  # above the fused rows' capacity (gs_plan_scap): three launches on every frame
+        assert largest + largest // 4 > GS_FUSED_MAX_SCAP
+        assert largest > 8 * 256 and (grid > 1024).sum() >= 2  # more than eight staged batches
+    else:  # the second frame of a context is fused
+        assert max(256, largest + largest // 4) <= GS_FUSED_MAX_SCAP
+    if name in ("field", "layers"):
+        assert largest > GS_MID and (grid > GS_MID).sum() >= 2  # the next frame plans the large-tile sort
+        assert (grid > 256).sum() > (grid > GS_MID).sum()  # and lists sorted inside the blend remain
+        assert per_tile <= 8  # (the host's tile order: well inside the policy's limit)
+    if name == "field":
+        assert (gx, gy) == (20, 12) and H % 16 and grid[-1].max() > 0  # the bottom row partial and populated
+        assert f["K"] > 30000 and largest > 3 * 256  # more than three staged batches
+        assert (n + 255) // 256 > 4 and (f["radii"] > 0).sum() > 4 * 256  # the projection backward's workgroups
+    if name == "layers":
+        assert np.count_nonzero(c["g"]["opacities"] == 1.0) > 1000
+        stopped = sum(int((t["first"] < t["n"]).any()) for t in c["r64"]["tiles"])
+        assert c["r64"]["stopped"] > 1000 and stopped > 16  # pixels that stop: in quantity, in many tiles
+        assert c["r64"]["clamped"] > 100
+    if name == "wide":
+        assert (gx, gy) == (125, 3) and W % 16 == 8
+        assert grid[:, gx - 2].max() >= 257  # the last full tile column: a second staged batch
+        assert grid[:, gx - 1].max() > 0  # the partial tile column
+        assert grid[:, 64:].max() > 0 and grid[:, 63].max() > 0 and grid[:, 0].max() > 0
+    if name == "tall":
+        assert (gx, gy) == (3, 69) and H % 16 == 8
+        assert grid[gy - 1].max() >= 257 and grid[gy - 2].max() >= 257  # the last (partial) tile row, the last full one
+        assert grid[64:].max() > 0 and grid[0].max() > 0
+    if name in ("wide", "tall"):
+        view = np.asarray(c["ubo"].view, np.float64).reshape(4, 4).T
+        assert np.abs(view[:3, :3]).min() > 0.1 and np.abs(view[:3, 3]).min() > 0.1  # a general view
+
+
+def test_frame_case_mask(frame_case):
+    """The masked share is at most 1% of the pixels (a cap), the upstream gradient is exactly 0 there, and the
+    float64 reference reports no borderline decision on a pixel with a non-zero upstream gradient."""
+    c = frame_case
+    share = float(c["mask"].mean())
+    print(f"{c['name']}: masked {int(c['mask'].sum())} of {c['mask'].size} pixels ({100 * share:.2f}%), borderline "
+          f"decisions {c['r64']['borderline']} (float32 run: {c['r32']['borderline']})")
+    assert c["mask"].shape == (c["H"], c["W"]) and share <= R.MASK_CAP
+    assert not np.any(c["dL"][c["mask"]]) and np.all(np.any(c["dL"][~c["mask"]] != 0.0, -1))
+    live = np.any(c["dL"] != 0.0, -1)
+    assert not np.any(c["r64"]["border_pixels"] & live)
+    assert np.array_equal(c["r64"]["border_pixels"], c["mask"])  # (the decisions do not depend on dL)
+    assert (c["r64"]["borderline"] > 0) == bool(c["mask"].any())
+
+
+def test_frame_reference_image_matches_the_oracle(frame_case):
+    keep = ~frame_case["mask"]
+    err = R.rel_l2(frame_case["r64"]["image"][keep], frame_case["frame"]["image"][keep])
+    print(f"{frame_case['name']}: float64 reference vs oracle image outside the mask rel L2 {err:.2e}")
+    assert err < 1e-4, err
+
+
+def test_frame_float32_reference_error(frame_case):
+    """e32 per key: printed. The GPU bound max(1e-4, 8 e32) follows it, also where float32 resolves a pixel
+    coordinate to 1.2e-4 only."""
+    for k in R.GRAD_KEYS:
+        ref = frame_case["r64"]["grads"][k]
+        assert np.isfinite(ref).all() and np.linalg.norm(ref) > 0
+        assert np.isfinite(frame_case["r32"]["grads"][k]).all()
+        print(f"{frame_case['name']} {k}: e32 {R.rel_l2(frame_case['r32']['grads'][k], ref):.2e}")
+
+
+def test_projection_backward_on_the_host_frames(frame_case, project_backward_bin, tmp_path):
+    """test_projection_backward_on_the_host on the frame cases: up to 20000 Gaussians, 2D means up to 2000 px."""
+    _host_projection_backward(frame_case, project_backward_bin, tmp_path)
 
 
 def test_backward_entry_point_is_exported(native_lib):
