@@ -988,7 +988,12 @@ int ptgs_splat_reserve(ptgs_ctx* ctx, uint32_t pairs);
  * Gaussian whose view depth is >= depth[pixel] (the mesh occludes it and everything behind), and
  * out = C + T * under (all four channels, C.a = 1 - T). depth: device float[W*H] (e.g. from
  * ptgs_trace_depth); under: device RGBA32F[W*H] (e.g. the ptgs_trace_camera accumulator); out may
- * alias under. Integer outputs (keys, values, ranges) are those of ptgs_splat_gaussians. */
+ * alias under, for calls with stats too, whether the call re-runs its frame or not: such a call
+ * composites over under as the caller passed it, through a copy the context keeps (W*H*16 bytes,
+ * taken in stream order when the two ranges overlap at all; calls without stats, and calls whose out is
+ * apart from under, copy nothing). A call without stats blends once, each pixel reading under before
+ * it writes out: there out is under itself or does not overlap it.
+ * Integer outputs (keys, values, ranges) are those of ptgs_splat_gaussians. */
 int ptgs_splat_gaussians_over(ptgs_ctx* ctx, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t width,
                               uint32_t height, const float* depth, const float* under_rgba32f,
                               uint32_t tile_row_begin, uint32_t tile_row_end, float* out_rgba32f,

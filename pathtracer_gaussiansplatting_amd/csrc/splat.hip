@@ -86,6 +86,7 @@ struct GsCall {
   uint32_t nwg_fused;  // the fused front end's owner workgroups (bands x 256-Gaussian chunks)
   uint32_t* order;     // the blend's tile order (heaviest tiles of the previous frame first; null: no rows)
   uint32_t scap;       // the fused rows' capacity (0: three launches)
+  const float* under;  // the `over` composite's image: the caller's, or the workspace's copy of it (gs_keep_under)
 };
 
 static hipError_t gs_mark(const GsCall& c, int k) {
@@ -205,6 +206,22 @@ static hipError_t gs_size_pools(const GsCall& c, uint32_t report) {
   return hipSuccess;
 }
 
+// Stage 4, last: the `over` composite of a call with stats whose `under` overlaps `out` (every hybrid caller
+// composites in place). Stage 6 may enqueue the blend again, and a second blend would read the first one's
+// result as `under` and composite the Gaussians twice: every blend of such a call reads a copy of `under`
+// taken here, in stream order before the first. Calls without stats blend once: no copy, nothing enqueued.
+static hipError_t gs_keep_under(GsCall& c) {
+  const SplatArgs& a = *c.a;
+  c.under = a.under;
+  if (!gs_plan_under_copy(a.stats != nullptr, a.under, a.out, a.W, a.H)) return hipSuccess;
+  const size_t bytes = (size_t)a.W * a.H * 16;
+  hipError_t e;
+  if ((e = c.w->under_copy.ensure(bytes, 0))) return e;  // (an image's size: no headroom)
+  if ((e = hipMemcpyAsync(c.w->under_copy.p, a.under, bytes, hipMemcpyDeviceToDevice, c.s))) return e;
+  c.under = (const float*)c.w->under_copy.p;
+  return hipSuccess;
+}
+
 // Stage 5, first: the front ends' per-Gaussian arguments and the buffers only they use
 static hipError_t gs_front_end_args(GsCall& c) {
   SplatWorkspace* w = c.w;
@@ -318,7 +335,7 @@ static hipError_t gs_blend(const GsCall& c, uint32_t cap, const GsFused& fu, uns
   hipLaunchKernelGGL(k, grid, dim3(GS_BLOCK), 0, c.s, c.cam, (const uint2*)w->ranges.p, (unsigned long long*)w->pairs.p,
                      sort_large ? (uint32_t)GS_MID : 0xFFFFFFFFu, keys_out, (uint32_t*)w->vals_out.p,
                      (const float4*)w->rec.p, a.bg[0], a.bg[1], a.bg[2], cap, c.slot_keys,
-                     (const unsigned long long*)w->tile_slots.p, a.depth, (const float4*)a.under, (float4*)a.out, fu, sp);
+                     (const unsigned long long*)w->tile_slots.p, a.depth, (const float4*)c.under, (float4*)a.out, fu, sp);
   const hipError_t le = hipGetLastError();
   if (!le && a.seq && fu.seq_flag) a.seq->launched = true;
   return le;
@@ -580,6 +597,7 @@ hipError_t splat_gaussians(SplatWorkspace* w, const SplatArgs& a, uint32_t* repo
   if ((e = gs_ensure_buffers(c))) return e;
   if ((e = gs_collect_reports(c, report))) return e;
   if ((e = gs_size_pools(c, *report))) return e;
+  if ((e = gs_keep_under(c))) return e;
   // 5. the front end (gs_plan_scap, from the latest frame's touched runs and largest tile) and the frame
   if ((e = gs_front_end_args(c))) return e;
   c.scap = gs_plan_scap(gs_env_frontend(), w->k_host[GS_KH_RUNS], w->have_hint, c.n, c.tiles, w->k_host[GS_KH_MAX_TILE]);

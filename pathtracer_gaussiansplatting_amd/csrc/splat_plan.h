@@ -207,6 +207,17 @@ inline uint32_t gs_plan_scap(int frontend, uint32_t touched_runs, bool have_hint
   return scap;
 }
 
+// The `over` composite ends each pixel with out = C + T * under, and a call with stats may enqueue its blend
+// more than once (splat.hip, gs_wait_and_rerun: a fused frame above its rows, a three-launch frame above the
+// pair buffer). Where the W * H RGBA32F ranges of `under` and `out` overlap at all, a second blend would read
+// the first one's result as `under`: such a call blends over a copy of `under` taken before its first blend.
+// A frame without stats blends once and copies nothing; without `under` there is nothing to keep.
+inline bool gs_plan_under_copy(bool stats, const void* under, const void* out, uint32_t W, uint32_t H) {
+  if (!stats || !under) return false;
+  const uintptr_t u = (uintptr_t)under, o = (uintptr_t)out;
+  return (u > o ? u - o : o - u) < (uint64_t)W * H * 16u;  // (the distance, not u + bytes: no wrap)
+}
+
 // Helper workgroups per band only when the latest fused frame queued slices (a static view whose chunks
 // all fit one slice launches none; the owners walk any slice no helper takes, so a frame that queues more
 // than the helpers take is complete anyway). Idle helpers polled the queue until every owner had

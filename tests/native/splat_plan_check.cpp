@@ -1,6 +1,6 @@
 // splat_plan_check.cpp — csrc/splat_plan.h (the 3DGS forward pass's host planning) built for the host alone:
-// pinned plans of the benchmark's frames, the edges of the kernels' static limits, and the invariants the
-// kernels rely on over a seeded sweep. Stand-alone (ASan + UBSan linked in by tests/test_splat_plan.py);
+// pinned plans of the benchmark's frames, the edges of the kernels' static limits, the rule for when an `over`
+// call keeps a copy of `under`, and the invariants the kernels rely on over a seeded sweep. Stand-alone (ASan + UBSan linked in by tests/test_splat_plan.py);
 // prints the first failed check and exits 1.
 #include <cstdio>
 #include <cstdlib>
@@ -138,6 +138,52 @@ static void check_spill(uint32_t n, uint32_t cap, uint32_t demand, bool inc, uin
   CHECK(gs_spill_capacity((size_t)want * 8, (size_t)want * 4) == want, "capacity of %llu", (unsigned long long)want);
 }
 
+// gs_plan_under_copy: a call with stats keeps a copy of `under` exactly when its W * H * 16 bytes overlap `out`'s
+static void check_under_copy(uintptr_t under, uintptr_t out, uint32_t W, uint32_t H) {
+  const uint64_t bytes = (uint64_t)W * H * 16u;
+  bool overlap = false;  // (restated with 128-bit ends: no wrap at the top of the address space)
+  if (under) {
+    const unsigned __int128 u0 = under, u1 = u0 + bytes, o0 = out, o1 = o0 + bytes;
+    overlap = u0 < o1 && o0 < u1;
+  }
+  const void* pu = (const void*)under;
+  const void* po = (const void*)out;
+  CHECK(gs_plan_under_copy(true, pu, po, W, H) == overlap, "under %llx out %llx %u x %u", (unsigned long long)under,
+        (unsigned long long)out, W, H);
+  CHECK(gs_plan_under_copy(true, po, pu, W, H) == (overlap && out != 0), "swapped: under %llx out %llx %u x %u",
+        (unsigned long long)out, (unsigned long long)under, W, H);
+  CHECK(!gs_plan_under_copy(false, pu, po, W, H), "a copy without stats");
+  CHECK(!gs_plan_under_copy(true, nullptr, po, W, H) && !gs_plan_under_copy(false, nullptr, po, W, H), "a copy without `under`");
+}
+
+static void under_copy_cases() {
+  const uint32_t W = 1920, H = 1080;
+  const uintptr_t bytes = (uintptr_t)W * H * 16u, base = 0x7f0000000000ull;
+  check_under_copy(base, base, W, H);              // in place: every hybrid caller
+  check_under_copy(base, base + 16, W, H);         // one pixel apart, from either side (the check swaps them too)
+  check_under_copy(base, base + bytes / 2, W, H);
+  check_under_copy(base, base + bytes - 1, W, H);  // the last byte
+  check_under_copy(base, base + bytes, W, H);      // adjacent: no overlap
+  check_under_copy(base + bytes, base, W, H);
+  check_under_copy(base, base + bytes + 16, W, H);
+  check_under_copy(base, base + (1ull << 40), W, H);
+  CHECK(gs_plan_under_copy(true, (const void*)base, (const void*)base, W, H), "in place");
+  CHECK(gs_plan_under_copy(true, (const void*)(base + bytes - 16), (const void*)base, W, H) &&
+            gs_plan_under_copy(true, (const void*)base, (const void*)(base + bytes - 16), W, H),
+        "the last pixel overlaps the first, from either side");
+  CHECK(!gs_plan_under_copy(true, (const void*)(base + bytes), (const void*)base, W, H) &&
+            !gs_plan_under_copy(true, (const void*)base, (const void*)(base + bytes), W, H),
+        "adjacent ranges");
+  CHECK(!gs_plan_under_copy(false, (const void*)base, (const void*)base, W, H), "no stats: one blend, no copy");
+  CHECK(!gs_plan_under_copy(true, nullptr, (const void*)base, W, H), "no `under`: a plain frame");
+  CHECK(!gs_plan_under_copy(true, (const void*)base, (const void*)base, 0, H), "an empty image");
+  // ranges that end at the top of the address space, and images beyond 4 GiB
+  check_under_copy(~(uintptr_t)0 - bytes + 1, ~(uintptr_t)0 - 2 * bytes + 1, W, H);
+  check_under_copy(~(uintptr_t)0 - 15, 16, 1, 1);
+  check_under_copy(base, base + (1ull << 33), 131072, 8192);
+  check_under_copy(base, base + (1ull << 34), 131072, 8192);
+}
+
 static void pinned() {
   BinGrid g;
   SplatCam cam = cam_of(1920, 1080);
@@ -265,6 +311,12 @@ static void sweep(uint32_t rounds) {
     if (r1 >= r0) CHECK(cam.row_end == std::min(r1, gy), "cam row_end %u", cam.row_end);
     CHECK(cam.rowcull == (cam.row_begin > 0 || cam.row_end < gy ? 1u : 0u) && cam.cull == (bounds && cam.rowcull ? 1u : 0u), "cam culls");
     CHECK(cam.tight == (((!stats && !publish) || (publish && tight)) ? 1u : 0u), "cam tight");
+    {  // `under` at random distances from `out`, around the image's size
+      const uint64_t bytes = (uint64_t)W * H * 16u;
+      const uintptr_t u = (uintptr_t)(0x100000000000ull + (rnd() & 0xFFFFFFFFFF0ull));
+      const uint64_t dist = rnd_below(4) ? rnd() % (2 * bytes + 16) : bytes + rnd_below(3) - 1;
+      check_under_copy(u, rnd_below(2) ? u + (uintptr_t)dist : u - (uintptr_t)dist, W, H);
+    }
     const bool ok = gs_plan_grid(cam, n, &g);
     const uint64_t tiles = (uint64_t)cam.grid_x * cam.grid_y;
     CHECK(ok == (cam.grid_x <= GS_BAND_TILES && (tiles + 63) / 64 <= GS_MAX_GROUPS), "accepted %d: %u x %u tiles", ok, cam.grid_x, cam.grid_y);
@@ -289,6 +341,7 @@ int main(int argc, char** argv) {
   const uint32_t rounds = argc > 1 ? (uint32_t)std::strtoul(argv[1], nullptr, 10) : 200000u;
   pinned();
   edges();
+  under_copy_cases();
   sweep(rounds);
   if (g_fail) return 1;
   std::printf("ok: %u sweep rounds\n", rounds);

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import adam_ref as A
-from pathtracer_gaussiansplatting_amd import DensifyStats, GaussianAdam, PtgsError, Renderer, _abi, densify_and_prune
+from pathtracer_gaussiansplatting_amd import DensifyStats, GaussianAdam, PtgsError, _abi, densify_and_prune
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -397,16 +397,11 @@ LEARNING_RATES = {"means": 1e-3, "log_scales": 5e-3, "rotations": 1e-3, "opacity
 PERCENT_DENSE = 0.01
 
 
-@pytest.fixture(scope="module")
-def trainer(renderer):
-    """A context of its own for the two tests that render. This file runs before test_configs_gpu.py, whose C4
-    hybrid frame (1M Gaussians, 1920 x 1080, `over`) comes out wrong on a context whose previous frame was a small
-    published one: the forward pass sizes its buffers from the workspace's previous frame. That is so without this
-    file too (test_densify_gpu.py::test_accumulate_through_splat_sh followed by the C4 test fails alike); the
-    session's context is therefore left without a frame here."""
-    r = Renderer(0, publish_splat_buffers=True)
-    yield r
-    r.close()
+# The two tests that render use the session's context. They once had one of their own: this file runs before
+# test_configs_gpu.py, whose C4 hybrid frame (1M Gaussians, 1920 x 1080, `over` in place, with stats) came out
+# wrong after a small published frame. The cause was not the buffers' sizes: such a frame leaves small fused rows,
+# the C4 frame overflowed them and was re-run inside its call, and the second blend composited over the first
+# one's result. A call with stats now blends over a copy of `under` (tests/test_splat_over_gpu.py).
 
 
 def _frame_radii(renderer, n):
@@ -418,11 +413,10 @@ def _frame_radii(renderer, n):
     return radii
 
 
-def test_gaussian_adam_one_step_from_a_backward(trainer):
+def test_gaussian_adam_one_step_from_a_backward(renderer):
     """One backward of autograd.splat_sh on the `batches` checkpoint (N = 520), then a dense step: bit for bit the
     reference applied to those .grad tensors; and a masked step with the frame's radii from the same state leaves
     the Gaussians of radius 0 untouched."""
-    renderer = trainer
     import test_sh_backward_gpu as B
     p, g, ubo, W, H, bg, dL = B._checkpoint_case("batches")
     n = len(p["means"])
@@ -491,12 +485,11 @@ def test_gaussian_adam_one_step_from_a_backward(trainer):
     assert opt2.lr["means"] == 0.5
 
 
-def test_gaussian_adam_densify_reset_adam(trainer):
+def test_gaussian_adam_densify_reset_adam(renderer):
     """test_adam_densify_adam of test_densify_gpu.py with GaussianAdam, the DC term at its own rate and the masked
     step: 15 steps with the statistic, densify_and_prune at the statistic's median, reset_opacity(0.01), 15 more
     steps. Measured: loss 22.2530 -> 8.8953, then (520 -> 781 Gaussians, every opacity at most 0.01) 174.0835 ->
     151.7356."""
-    renderer = trainer
     import densify_ref as D
     import test_sh_backward_gpu as B
     lr = LEARNING_RATES
