@@ -537,7 +537,7 @@ typedef struct ptgs_gaussians {
 typedef struct ptgs_splat_stats {
     uint32_t num_rendered; /* K = (gaussian, tile) pairs */
     uint32_t tiles_x, tiles_y;
-    uint32_t num_visible;  /* gaussians with radius > 0 */
+    uint32_t num_visible;  /* not counted: always 0 (count radii > 0 from ptgs_splat_get_buffers) */
     uint32_t fused;        /* 1: the frame ran the single-launch front end (gs_bin_fused_kernel), 0: count +
                             * column scan + scatter */
 } ptgs_splat_stats;

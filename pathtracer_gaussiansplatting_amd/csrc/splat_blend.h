@@ -193,9 +193,13 @@ __global__ __launch_bounds__(GS_BLOCK, GS_BLEND_MIN_BLOCKS) void gs_sort_blend_k
   }
   STAMP(1, 4);
   const float tx0 = (float)(tile_x * GS_BLOCK_X), ty0 = (float)(tile_y * GS_BLOCK_Y);
-  // Stage a record as the quadratic in tile-local pixel coordinates (ux, uy):
-  // z = A ux^2 + B ux uy + C uy^2 + D ux + E uy + F (five FMAs per evaluation instead of seven), and
-  // return the quadrant mask of its alpha box: bit q = (x half q & 1, y half q >> 1), the box tested
+  // Stage a record with its 2D mean in tile-local pixel coordinates (gx, gy): the blend evaluates
+  // z = A dx^2 + B dx dy + C dy^2 + log2 o from (dx, dy) = pixel - mean, the form in which ptgs.h states the
+  // function. (Until tests/test_splat_forward_gpu.py the record held the quadratic expanded in (ux, uy),
+  // A ux^2 + B ux uy + C uy^2 + D ux + E uy + F, five FMAs instead of seven operations: for a Gaussian that is all
+  // dilation, conic 1 / 0.3, F and D ux reach 1 200 inside the tile and cancel to a z of a few units, up to 1e-4
+  // in z and 5e-5 in a pixel; the expansion now serves the exact quadrant test below alone, whose 0.02 margin
+  // covers that.) Return the quadrant mask of its alpha box: bit q = (x half q & 1, y half q >> 1), the box tested
   // in tile-local coordinates against the quadrants' pixel ranges [0, 7] / [8, 15] (immediates: no
   // register holds a tile bound across the batch loop; the box's 1% + 0.01 px margin covers the
   // rounding of the local shift). exact: also the exact quadrant test (small tiles; the large-tile batch
@@ -204,8 +208,8 @@ __global__ __launch_bounds__(GS_BLOCK, GS_BLEND_MIN_BLOCKS) void gs_sort_blend_k
     const float gx = ga.x - tx0, gy = ga.y - ty0, A = ga.z, B = ga.w, C = gb.x;
     const float D = -2.0f * A * gx - B * gy, E = -B * gx - 2.0f * C * gy;
     const float F = ((A * gx * gx + B * gx * gy) + C * gy * gy) + gb.y;
-    s_stage[slot].a = make_float4(A, B, C, D);
-    s_stage[slot].b = make_float4(E, F, gb.z, gb.w);
+    s_stage[slot].a = make_float4(A, B, C, gx);
+    s_stage[slot].b = make_float4(gy, gb.y, gb.z, gb.w);
     s_stage[slot].c = gc;
     const float x0 = gx - gc.y, x1 = gx + gc.y, y0 = gy - gc.z, y1 = gy + gc.z;
     const bool xl = x0 <= 7.0f && x1 >= 0.0f, xr = x0 <= 15.0f && x1 >= 8.0f;
@@ -406,7 +410,7 @@ __global__ __launch_bounds__(GS_BLOCK, GS_BLEND_MIN_BLOCKS) void gs_sort_blend_k
   // the per-entry validity and the every-4-entries all-done test read it without moving it into a VGPR
   unsigned long long done = __builtin_amdgcn_ballot_w64(!inside);
   const float pfx = (float)px, pfy = (float)py;
-  const float ux = pfx - tx0, uy = pfy - ty0, uxx = ux * ux, uxy = ux * uy, uyy = uy * uy;
+  const float ux = pfx - tx0, uy = pfy - ty0;
   const float lim = (OVER && inside) ? depth_lim[(size_t)py * cam.W + px] : 0.0f;
   float T = 1.0f;
   float C0 = 0.0f, C1 = 0.0f, C2 = 0.0f;
@@ -474,12 +478,11 @@ __global__ __launch_bounds__(GS_BLOCK, GS_BLEND_MIN_BLOCKS) void gs_sort_blend_k
           const float gd = *reinterpret_cast<const float*>(stage + o + 44);
           done |= __builtin_amdgcn_ballot_w64(!(gd < lim));
         }
-        // z = A dx^2 + B dx dy + C dy^2 + log2 o as staged: a quadratic in the tile-local (ux, uy), five
-        // FMAs (the centre-relative form costs seven; the expansion's rounding is ~1e-6 in z). (The
-        // reference's power > 0 skip is not tested: the conic is positive definite (+0.3 low-pass),
-        // so power <= 0 up to rounding at power ~ 0.)
-        const float z = __builtin_fmaf(a.x, uxx, __builtin_fmaf(a.y, uxy, __builtin_fmaf(a.z, uyy,
-                                       __builtin_fmaf(a.w, ux, __builtin_fmaf(b.x, uy, b.y)))));
+        // z = A dx^2 + B dx dy + C dy^2 + log2 o at (dx, dy) = pixel - mean, both tile-local: two subtractions,
+        // two multiplies, three FMAs. (The reference's power > 0 skip is not tested: the conic is positive
+        // definite (+0.3 low-pass), so power <= 0 up to rounding at power ~ 0.)
+        const float dx = ux - a.w, dy = uy - b.x;
+        const float z = __builtin_fmaf(__builtin_fmaf(a.x, dx, a.y * dy), dx, __builtin_fmaf(a.z * dy, dy, b.y));
         // alpha >= 1/255: z >= log2(1/255)
         const bool valid = __builtin_amdgcn_inverse_ballot_w64(__builtin_amdgcn_ballot_w64(z >= -7.9943534f) & ~done);
         const float alpha = valid ? fminf(0.99f, __builtin_amdgcn_exp2f(z)) : 0.0f;
