@@ -6,9 +6,9 @@
 //   1. blend backward   one workgroup per 16x16 tile, one pixel per lane (the forward's quadrant-per-wave
 //                       mapping). The records are staged through LDS in batches of 256; z = A dx^2 + B dx dy +
 //                       C dy^2 + log2 o is evaluated from (dx, dy) = pixel - 2D mean, and the alpha >= 1/255
-//                       skip and the T < 1e-4 stop are the forward's tests on it (the forward's z, the same
-//                       quadratic expanded in tile-local coordinates, differs by its rounding: about 3e-5 of
-//                       alpha). Two front-to-back walks: the first recomputes what the forward
+//                       skip and the T < 1e-4 stop are the forward's tests on it (the forward takes z from
+//                       pixel - mean as well, splat_blend.h; the two differ by the grouping of their FMAs
+//                       alone). Two front-to-back walks: the first recomputes what the forward
 //                       does not keep (the pixel's T_final and, folded into one number, the whole sum
 //                       dL/dC . C + dL/dT_final T_final); the second walks again with the prefix of that
 //                       sum, which gives each pair's suffix without a division by 1 - alpha per step, and
@@ -18,8 +18,9 @@
 //                       the pairs whose alpha box reaches its quadrant, and skips by ballot a pair none of
 //                       its lanes evaluates.
 //   2. project backward one work-item per Gaussian: the accumulator -> colours, opacity, (2D mean, conic)
-//                       and, through conic = cov^-1, cov = T Sigma T^T + 0.3 I, T = J W, Sigma = R S^2 R^T,
-//                       q / |q|, the 3D mean, the scales and the rotation. Plain f32.
+//                       and, through conic = cov^-1, cov = A A^T + 0.3 I, A = T R S, T = J W, q / |q|, the
+//                       3D mean, the scales and the rotation. Plain f32, one column of A at a time
+//                       (splat_backward_math.h says why).
 // Float atomics: the sums depend on the arrival order, so the gradients are not bit-reproducible.
 //
 // Depth supervision rides in the same walks. The expected inverse depth D = sum alpha T / d of a pixel is
@@ -73,11 +74,11 @@ __device__ __forceinline__ void gb_stage_batch(uint32_t tid, uint32_t idx, uint3
     const uint32_t g = vals[first + idx];
     const float4 ga = rec[3 * g], gb = rec[3 * g + 1], gc = rec[3 * g + 2];
     // the record's quadratic and the 2D mean in tile-local pixel coordinates. z is evaluated from
-    // (dx, dy) = pixel - mean, as ptgs.h states the function, not from the forward's expansion into
-    // A ux^2 + ... + F: there terms of several hundred cancel to a z of a few units, an error of 3e-5
-    // in alpha that the forward's 1e-4 allowance covers but that reached 1.5e-4 relative L2 in the
-    // gradients of the quarter of a case's Gaussians with the smallest ones (5e-6, float32 autograd's
-    // own error there, in this form)
+    // (dx, dy) = pixel - mean, as ptgs.h states the function and as the forward's blend evaluates it, not
+    // from the quadratic expanded into A ux^2 + ... + F: there terms of several hundred cancel to a z of
+    // a few units, an error of 3e-5 in alpha that reached 1.5e-4 relative L2 in the gradients of the
+    // quarter of a case's Gaussians with the smallest ones (5e-6, float32 autograd's own error there, in
+    // this form). The forward keeps the expansion for its exact quadrant test alone.
     const float gx = ga.x - tx0, gy = ga.y - ty0;
     s_stage[3 * tid] = make_float4(ga.z, ga.w, gb.x, gb.y);
     s_stage[3 * tid + 1] = make_float4(0.0f, 0.0f, gb.z, gb.w);

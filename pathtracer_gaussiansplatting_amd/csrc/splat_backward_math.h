@@ -17,7 +17,18 @@ struct GbCam {
 
 // One visible Gaussian: (dL/d means2d (dgx, dgy), dL/d conic (da, db, dc)) -> dL/d mean (dm), the linear
 // scales (dsc) and the un-normalised quaternion (dq), through conic = cov^-1, cov = T Sigma T^T + 0.3 I,
-// T = J W with J at the clamped point, Sigma = R S^2 R^T and q / |q| (gs_preprocess_one's forward, recomputed).
+// T = J W with J at the clamped point, Sigma = R S^2 R^T and q / |q| (gs_preprocess_one's function).
+//
+// The covariance is handled as cov = A A^T + 0.3 I, A = T R S (2x3), one column A_k = sc[k] T R[:, k] at a time,
+// and neither Sigma nor Mc = dL/dcov = -Q G Q is formed. With Mc built from the rounded conic Q and carried
+// through T^T Mc T Sigma, the gradient of a needle's long axis (axis ratio 200 and more) was what is left when
+// terms (l1 / l2) times larger cancel, l1, l2 the eigenvalues of cov: 6e-3 relative in a single dL/dsc, 1.8e-4
+// relative L2 over a case, 10x float32 autograd's error, and no single stage in double repaired it. Here
+//   Q A_k = adj(cov) A_k / det = adj(cov - A_k A_k^T) A_k / det,  since adj is linear on 2x2 matrices and
+//   adj(A_k A_k^T) A_k = 0 exactly: the long axis meets only the other two columns and the dilation;
+//   det(A A^T + 0.3 I) = |row 0 x row 1|^2 + 0.3 tr(A A^T) + 0.09 (Cauchy-Binet): a sum of positive terms;
+//   dL/dA_k = -2 Q G (Q A_k), dL/dsc[k] = -2 sc[k] (Q t_k)^T G (Q t_k) with t_k = T R[:, k].
+// The same case then lands at 7e-6, under float32 autograd's error.
 // DEPTH: dinvd = dL/d(1/d) as well, the inverse depth's share (D = sum wgt / d): it reaches the mean through
 // d = -(V row 2) . (mean, 1) alone, dL/dd = -dinvd / d^2. Order and membership carry no gradient.
 template <bool DEPTH = false>
@@ -43,15 +54,6 @@ PTGS_HD void gs_project_backward_one(const GbCam& cam, const float* mean, const 
                          {2.0f * (qx * qy + qr * qz), 1.0f - 2.0f * (qx * qx + qz * qz), 2.0f * (qy * qz - qr * qx)},
                          {2.0f * (qx * qz - qr * qy), 2.0f * (qy * qz + qr * qx), 1.0f - 2.0f * (qx * qx + qy * qy)}};
   const float sc[3] = {sx, sy, sz};
-  float M[3][3], S[3][3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) M[r][k] = R[r][k] * sc[k];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) S[r][k] = (M[r][0] * M[k][0] + M[r][1] * M[k][1]) + M[r][2] * M[k][2];
   const float txtz = pvx / d, tytz = pvy / d;
   const bool clx = txtz < -cam.limx || txtz > cam.limx, cly = tytz < -cam.limy || tytz > cam.limy;
   const float tx = fminx(cam.limx, fmaxx(-cam.limx, txtz)) * d;
@@ -65,47 +67,49 @@ PTGS_HD void gs_project_backward_one(const GbCam& cam, const float* mean, const 
     T[0][k] = J00 * Wm[0][k] + J02 * Wm[2][k];
     T[1][k] = J11 * Wm[1][k] + J12 * Wm[2][k];
   }
-  float U[2][3];  // T Sigma
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) U[r][k] = (T[r][0] * S[0][k] + T[r][1] * S[1][k]) + T[r][2] * S[2][k];
-  const float ca = ((U[0][0] * T[0][0] + U[0][1] * T[0][1]) + U[0][2] * T[0][2]) + 0.3f;
-  const float cb = (U[0][0] * T[1][0] + U[0][1] * T[1][1]) + U[0][2] * T[1][2];
-  const float cc = ((U[1][0] * T[1][0] + U[1][1] * T[1][1]) + U[1][2] * T[1][2]) + 0.3f;
-  const float det_inv = 1.0f / (ca * cc - cb * cb);
-  const float a = cc * det_inv, b = -cb * det_inv, c = ca * det_inv;  // the conic Q = cov^-1
-  // ---- conic -> cov: dL = tr(Mc dcov) with Mc = -Q G Q, G = [[da, db/2], [db/2, dc]] ----
-  const float hb = 0.5f * db;
-  const float g00 = a * da + b * hb, g01 = a * hb + b * dc, g10 = b * da + c * hb, g11 = b * hb + c * dc;
-  const float m00 = -(g00 * a + g01 * b), m01 = -(g00 * b + g01 * c), m11 = -(g10 * b + g11 * c);
-  // ---- cov = T Sigma T^T: dL/dSigma = T^T Mc T, dL/dT = 2 Mc T Sigma ----
-  float MT[2][3], N[3][3], dT[2][3];
+  // cov = A A^T + 0.3 I with A = T R S, column by column: column k is sc[k] (ux, uy)[k], the image of the
+  // Gaussian's axis k. Sigma = R S^2 R^T is never formed (see the note above the function).
+  float ux[3], uy[3], pxx[3], pxy[3], pyy[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    MT[0][k] = m00 * T[0][k] + m01 * T[1][k];
-    MT[1][k] = m01 * T[0][k] + m11 * T[1][k];
+    ux[k] = (T[0][0] * R[0][k] + T[0][1] * R[1][k]) + T[0][2] * R[2][k];
+    uy[k] = (T[1][0] * R[0][k] + T[1][1] * R[1][k]) + T[1][2] * R[2][k];
+    const float ax = ux[k] * sc[k], ay = uy[k] * sc[k];
+    pxx[k] = ax * ax;
+    pxy[k] = ax * ay;
+    pyy[k] = ay * ay;
   }
+  // det(A A^T + 0.3 I) = |row 0 x row 1|^2 + 0.3 tr(A A^T) + 0.09: positive terms only (Cauchy-Binet)
+  const float n01 = (ux[0] * uy[1] - ux[1] * uy[0]) * (sc[0] * sc[1]);
+  const float n02 = (ux[0] * uy[2] - ux[2] * uy[0]) * (sc[0] * sc[2]);
+  const float n12 = (ux[1] * uy[2] - ux[2] * uy[1]) * (sc[1] * sc[2]);
+  const float exx = (pxx[0] + pxx[1]) + pxx[2], exy = (pxy[0] + pxy[1]) + pxy[2], eyy = (pyy[0] + pyy[1]) + pyy[2];
+  const float det_inv = 1.0f / (((n01 * n01 + n02 * n02) + n12 * n12) + (0.3f * (exx + eyy) + 0.09f));
+  const float a = (eyy + 0.3f) * det_inv, b = -exy * det_inv, c = (exx + 0.3f) * det_inv;  // the conic Q = cov^-1
+  // ---- conic -> cov -> A: dL = tr(Mc dcov) with Mc = -Q G Q, G = [[da, db/2], [db/2, dc]]; dL/dA = 2 Mc A.
+  // Column k: Q A_k = sc[k] adj(B_k) (ux, uy)[k] / det with B_k = cov - A_k A_k^T, then G, then Q. ----
+  const float hb = 0.5f * db;
+  float dAx[3], dAy[3];
 #pragma unroll
-  for (int r = 0; r < 3; ++r)
+  for (int k = 0; k < 3; ++k) {
+    const int i = (k + 1) % 3, j = (k + 2) % 3;
+    const float bxx = (pxx[i] + pxx[j]) + 0.3f, bxy = pxy[i] + pxy[j], byy = (pyy[i] + pyy[j]) + 0.3f;
+    const float wx = (byy * ux[k] - bxy * uy[k]) * det_inv, wy = (bxx * uy[k] - bxy * ux[k]) * det_inv;
+    const float gx = da * wx + hb * wy, gy = hb * wx + dc * wy;
+    const float f = -2.0f * sc[k];
+    dsc[k] = f * (wx * gx + wy * gy);  // dL/dA_k . d A_k / d sc[k]
+    dAx[k] = (f * sc[k]) * (a * gx + b * gy);  // dL/dA_k times sc[k] (both uses below carry that factor)
+    dAy[k] = (f * sc[k]) * (b * gx + c * gy);
+  }
+  // ---- A = T R S: dL/dT = dL/dA (R S)^T, dL/dR = T^T dL/dA S ----
+  float dT[2][3], dR[3][3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) N[r][k] = T[0][r] * MT[0][k] + T[1][r] * MT[1][k];
+  for (int r = 0; r < 3; ++r) {
+    dT[0][r] = (dAx[0] * R[r][0] + dAx[1] * R[r][1]) + dAx[2] * R[r][2];
+    dT[1][r] = (dAy[0] * R[r][0] + dAy[1] * R[r][1]) + dAy[2] * R[r][2];
 #pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) dT[r][k] = 2.0f * ((MT[r][0] * S[0][k] + MT[r][1] * S[1][k]) + MT[r][2] * S[2][k]);
-  // ---- Sigma = M M^T, M = R S: dL/dM = 2 N M; scales and R ----
-  float dR[3][3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) dsc[k] = 0.0f;
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float dM = 2.0f * ((N[r][0] * M[0][k] + N[r][1] * M[1][k]) + N[r][2] * M[2][k]);
-      dsc[k] += dM * R[r][k];
-      dR[r][k] = dM * sc[k];
-    }
+    for (int k = 0; k < 3; ++k) dR[r][k] = T[0][r] * dAx[k] + T[1][r] * dAy[k];
+  }
   // ---- R(q / |q|) ----
   const float hr = 2.0f * (((-qz * dR[0][1] + qy * dR[0][2]) + (qz * dR[1][0] - qx * dR[1][2])) +
                            (-qy * dR[2][0] + qx * dR[2][1]));
