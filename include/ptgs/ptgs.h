@@ -43,7 +43,8 @@ extern "C" {
                              * structs), ptgs_image_loss_l1_dssim, ptgs_gaussians_adam_step,
                              * ptgs_gaussians_opacity_reset (with the structs ptgs_adam_rows and
                              * ptgs_adam_params), ptgs_splat_gaussians_invdepth,
-                             * ptgs_splat_gaussians_backward_depth, ptgs_image_loss_invdepth_l1;
+                             * ptgs_splat_gaussians_backward_depth, ptgs_image_loss_invdepth_l1,
+                             * ptgs_splat_gaussians_backward_pose, ptgs_gaussians_sh_colors_backward_eye;
                              * ptgs_read_gaussian_ply in ptgs_host.h */
 
 /* ---------------- error codes ---------------- */
@@ -661,6 +662,22 @@ int ptgs_gaussians_activate(ptgs_ctx* ctx, const float* log_scales, const float*
 int ptgs_gaussians_sh_colors_backward(ptgs_ctx* ctx, const float* means, const float* sh, uint32_t count,
                                       uint32_t sh_degree, uint32_t active_degree, const float camera_pos[3],
                                       const float* dL_dcolors, float* dL_dsh, float* dL_dmeans, void* hip_stream);
+/* ptgs_gaussians_sh_colors_backward plus the gradient with respect to the eye: with SH colours the frame depends on
+ * the camera through camera_pos as well (the rasterizer itself does not read it), so a pose gradient of a
+ * checkpoint of degree >= 1 needs this term. dL_dsh and the addition into dL_dmeans (which may be null) are those
+ * of ptgs_gaussians_sh_colors_backward, bit for bit; in addition dL_dcamera_pos (device float[3]) is written:
+ *   dL_dcamera_pos = -sum_i (v_i - dir_i (dir_i . v_i)) / len_i
+ * the negative of the sum of what the call adds to dL_dmeans (formed with dL_dmeans == NULL too): the colour sees
+ * mean - camera_pos alone. A Gaussian at the eye adds nothing; with active_degree == 0, sh_degree == 0 or
+ * count == 0 three exact zeros are written. The sum has two stages: each workgroup of 256 Gaussians leaves one
+ * partial (f32, a fixed order), and a second launch on the stream adds the partials in float64 in a fixed order.
+ * No atomics: two runs give the same bits. Scratch for the partials (12 bytes per 256 Gaussians) belongs to the
+ * context; growing it may synchronise. PTGS_EINVAL as above, and for a null or non-device dL_dcamera_pos
+ * (nothing enqueued). */
+int ptgs_gaussians_sh_colors_backward_eye(ptgs_ctx* ctx, const float* means, const float* sh, uint32_t count,
+                                          uint32_t sh_degree, uint32_t active_degree, const float camera_pos[3],
+                                          const float* dL_dcolors, float* dL_dsh, float* dL_dmeans,
+                                          float* dL_dcamera_pos, void* hip_stream);
 /* Backward of ptgs_gaussians_activate from the ACTIVATED values (what the forward left: scales 3N, opacities
  * N): dL_dlog_scales = dL_dscales * scales, dL_dlogits = (dL_dopacities * o) * (1.0f - o); plain f32, no
  * FMA (checkable bit for bit). In place allowed (dL_dlog_scales == dL_dscales, dL_dlogits == dL_dopacities).
@@ -713,7 +730,8 @@ int ptgs_gaussians_permute_sh(ptgs_ctx* ctx, const float* sh, uint32_t sh_degree
  * published frame (above).
  * ptgs_gaussians_sh_colors_backward and ptgs_gaussians_activate_backward continue the chain from
  * grads.colors / means / scales / opacities to a checkpoint's SH coefficients, log-scales and logits.
- * Not covered: gradients with respect to the camera, the `over` composite, tile-row shards. */
+ * The gradient with respect to the camera pose is ptgs_splat_gaussians_backward_pose (below).
+ * Not covered: the `over` composite, tile-row shards. */
 typedef struct ptgs_gaussian_grads {
     float* means;      /* 3N */
     float* scales;     /* 3N, w.r.t. the linear scales */
@@ -755,6 +773,39 @@ int ptgs_splat_gaussians_backward_depth(ptgs_ctx* ctx, const ptgs_gaussians* g, 
                                         uint32_t width, uint32_t height, const float bg[3],
                                         const float* dL_dout_rgba32f, const float* dL_dinvdepth,
                                         const ptgs_gaussian_grads* grads, void* hip_stream);
+
+/* The camera-pose gradient (pose refinement, tracking, joint pose and scene optimisation).
+ * ptgs_splat_gaussians_backward_pose does everything ptgs_splat_gaussians_backward does, or
+ * ptgs_splat_gaussians_backward_depth when dL_dinvdepth != NULL (NULL: the loss depends on the image alone): the
+ * frame conditions, the grads outputs and the error paths are the same. In addition it writes dL_dview (device
+ * float[16]), column-major like ptgs_ubo.view: entry c * 4 + r is dL/d view[r][c].
+ * The function differentiated is the one stated above, read as a function of `view`:
+ *   (x, y, -d) = view * (mean, 1)
+ *   W is the upper-left 3x3 of view in T = J W
+ *   ph = (proj * view) * (mean, 1) with proj a constant (mvp is formed on the host; the gradient treats it as
+ *   that product)
+ *   fx, fy and the clamp limits are constants; the rasterizer does not read camera_pos
+ *   every discrete decision is held fixed, as before; a clamped tx depends on the view through d only
+ *   with dL_dinvdepth, 1 / d passes gradient to row 2 of view
+ *   row 3 of view is held at (0, 0, 0, 1): its four entries are written as exactly 0
+ * Per visible Gaussian, with mh = (mean, 1), dpx, dpy, dd = dL/d(x, y, d) and dph = dL/d ph, the twelve
+ * contributions are g_r * mh[c] (r < 3, c < 4) with
+ *   g = (dpx, dpy, -dd) + the first three entries of proj^T (dphx, dphy, 0, dphw)
+ * and the rotation block additionally gets J^T dT (dT = dL/dT): row 0 J00 dT[0][k], row 1 J11 dT[1][k], row 2
+ * J02 dT[0][k] + J12 dT[1][k]. A culled Gaussian contributes exactly 0.
+ * The sum over the Gaussians has two stages: each workgroup of 256 Gaussians leaves one partial of 12 floats
+ * (f32, a fixed order), and a second launch on the stream adds the partials in float64 in a fixed order and
+ * writes the 16 floats. It uses no atomics; dL_dview still inherits the run-to-run variation of the blend's
+ * per-Gaussian sums (above). Scratch (48 bytes per 256 Gaussians) belongs to the context's splat workspace and is
+ * grown like the other buffers; every partial read was written by the same call.
+ * count == 0: dL_dview is set to sixteen zeros, PTGS_OK. PTGS_EINVAL (nothing enqueued), besides the cases above:
+ * a null or non-device dL_dview.
+ * With SH colours the eye adds its own term: ptgs_gaussians_sh_colors_backward_eye.
+ * Not covered: gradients with respect to proj (the intrinsics). */
+int ptgs_splat_gaussians_backward_pose(ptgs_ctx* ctx, const ptgs_gaussians* g, const ptgs_ubo* ubo,
+                                       uint32_t width, uint32_t height, const float bg[3],
+                                       const float* dL_dout_rgba32f, const float* dL_dinvdepth,
+                                       const ptgs_gaussian_grads* grads, float* dL_dview, void* hip_stream);
 
 /* Densification and pruning of a training run (densify_and_prune of Kerbl et al.'s trainer, new Gaussians
  * inheriting the parent's screen radius), in three steps: a statistic accumulated after every backward, a

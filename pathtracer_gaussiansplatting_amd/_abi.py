@@ -277,6 +277,9 @@ SYMBOLS = {
     "ptgs_splat_gaussians_invdepth": (_I, [_P, _U, _U, _P, _P]),
     "ptgs_splat_gaussians_backward_depth": (_I, [_P, C.POINTER(Gaussians), C.POINTER(Ubo), _U, _U, _FP, _P, _P,
                                                  C.POINTER(GaussianGrads), _P]),
+    "ptgs_splat_gaussians_backward_pose": (_I, [_P, C.POINTER(Gaussians), C.POINTER(Ubo), _U, _U, _FP, _P, _P,
+                                                C.POINTER(GaussianGrads), _P, _P]),
+    "ptgs_gaussians_sh_colors_backward_eye": (_I, [_P, _P, _P, _U, _U, _U, _FP, _P, _P, _P, _P, _P]),
     "ptgs_densify_accumulate": (_I, [_P, _P, _P, _U, _U, _U, _P, _P, _P, _P]),
     "ptgs_gaussians_densify_plan": (_I, [_P, _P, _P, _P, _P, _P, _U, C.POINTER(DensifyParams),
                                          C.POINTER(DensifyCounts), _P]),

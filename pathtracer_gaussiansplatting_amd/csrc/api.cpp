@@ -34,6 +34,7 @@
 #include "pt_wavefront.h"
 #include "scene_flatten.h"
 #include "comm.h"
+#include "dev_buf.h"
 #include "splat.h"
 #include "splat_adam.h"
 #include "splat_adam_math.h"
@@ -63,6 +64,7 @@ struct ptgs_ctx {
   SplatFrames frames;  // the splat frame calls' workspaces, streams, events, run and pending reports
   DensifyWorkspace* densify = nullptr;  // the densification plan (ptgs_gaussians_densify_plan / _apply)
   LossWorkspace* loss = nullptr;  // the partial maps and sums of ptgs_image_loss_l1_dssim
+  ptgs::DevBuf sh_eye_partials;  // per-workgroup partial sums of ptgs_gaussians_sh_colors_backward_eye
   ptgs::WfWorkspace wf;  // wavefront path tracer buffers (PTGS_FLAG_PT_WAVEFRONT)
   ptgs::PtSched pt_sched;  // megakernel tile schedule (heavy tiles first)
   void* comm = nullptr;  // RCCL communicator (ptgs_comm_create)
@@ -1027,21 +1029,49 @@ int ptgs_gaussians_activate(ptgs_ctx* c, const float* log_scales, const float* o
   return hip_rc(c, e, "ptgs_gaussians_activate");
 }
 
-int ptgs_gaussians_sh_colors_backward(ptgs_ctx* c, const float* means, const float* sh, uint32_t count,
-                                      uint32_t sh_degree, uint32_t active_degree, const float camera_pos[3],
-                                      const float* dL_dcolors, float* dL_dsh, float* dL_dmeans, void* stream) {
+// ptgs_gaussians_sh_colors_backward and _backward_eye (eye: dL_dcamera_pos is written as well)
+static int sh_backward_call(ptgs_ctx* c, const float* means, const float* sh, uint32_t count, uint32_t sh_degree,
+                            uint32_t active_degree, const float camera_pos[3], const float* dL_dcolors, float* dL_dsh,
+                            float* dL_dmeans, bool eye, float* dL_dcamera_pos, void* stream, const char* name) {
   if (!c) return PTGS_EINVAL;
   if (sh_degree > 3) return fail(c, PTGS_EINVAL, "sh_degree %u above 3", sh_degree);
   if (active_degree > sh_degree)
     return fail(c, PTGS_EINVAL, "active_degree %u above the stored sh_degree %u", active_degree, sh_degree);
-  if (count == 0) return PTGS_OK;  // (empty arrays may be null)
+  if (eye && !dL_dcamera_pos) return fail(c, PTGS_EINVAL, "null argument (dL_dcamera_pos)");
+  if (eye && !is_device_ptr(dL_dcamera_pos)) return fail(c, PTGS_EINVAL, "dL_dcamera_pos is not a device pointer");
+  if (count == 0) {  // (empty arrays may be null)
+    if (!eye) return PTGS_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return hip_rc(c, hipMemsetAsync(dL_dcamera_pos, 0, 3 * sizeof(float), (hipStream_t)stream), name);
+  }
   if (!means || !sh || !camera_pos || !dL_dcolors || !dL_dsh) return fail(c, PTGS_EINVAL, "null argument");
   if (dL_dsh == sh) return fail(c, PTGS_EINVAL, "dL_dsh must not alias sh");
   if (!is_device_ptr(dL_dsh)) return fail(c, PTGS_EINVAL, "dL_dsh is not a device pointer");
   HIPCHK(c, hipSetDevice(c->device));
-  const hipError_t e = splat_sh_colors_backward(means, sh, count, sh_degree, active_degree, camera_pos, dL_dcolors,
-                                                dL_dsh, dL_dmeans, (hipStream_t)stream);
-  return hip_rc(c, e, "ptgs_gaussians_sh_colors_backward");
+  if (!eye)
+    return hip_rc(c, splat_sh_colors_backward(means, sh, count, sh_degree, active_degree, camera_pos, dL_dcolors,
+                                              dL_dsh, dL_dmeans, (hipStream_t)stream), name);
+  // (growth frees the old buffer, which waits for the device)
+  const size_t bytes = (size_t)splat_sh_eye_rows(count) * 3 * sizeof(float);
+  HIPCHK(c, c->sh_eye_partials.ensure(bytes, bytes / 4));
+  return hip_rc(c, splat_sh_colors_backward_eye(means, sh, count, sh_degree, active_degree, camera_pos, dL_dcolors,
+                                                dL_dsh, dL_dmeans, c->sh_eye_partials.as<float>(), dL_dcamera_pos,
+                                                (hipStream_t)stream), name);
+}
+
+int ptgs_gaussians_sh_colors_backward(ptgs_ctx* c, const float* means, const float* sh, uint32_t count,
+                                      uint32_t sh_degree, uint32_t active_degree, const float camera_pos[3],
+                                      const float* dL_dcolors, float* dL_dsh, float* dL_dmeans, void* stream) {
+  return sh_backward_call(c, means, sh, count, sh_degree, active_degree, camera_pos, dL_dcolors, dL_dsh, dL_dmeans,
+                          false, nullptr, stream, "ptgs_gaussians_sh_colors_backward");
+}
+
+int ptgs_gaussians_sh_colors_backward_eye(ptgs_ctx* c, const float* means, const float* sh, uint32_t count,
+                                          uint32_t sh_degree, uint32_t active_degree, const float camera_pos[3],
+                                          const float* dL_dcolors, float* dL_dsh, float* dL_dmeans,
+                                          float* dL_dcamera_pos, void* stream) {
+  return sh_backward_call(c, means, sh, count, sh_degree, active_degree, camera_pos, dL_dcolors, dL_dsh, dL_dmeans,
+                          true, dL_dcamera_pos, stream, "ptgs_gaussians_sh_colors_backward_eye");
 }
 
 int ptgs_gaussians_activate_backward(ptgs_ctx* c, const float* scales, const float* opacities, uint32_t count,
@@ -1073,14 +1103,23 @@ int ptgs_gaussians_permute_sh(ptgs_ctx* c, const float* sh, uint32_t sh_degree, 
   return hip_rc(c, e, "ptgs_gaussians_permute_sh");
 }
 
-// ptgs_splat_gaussians_backward (depth == false: dL_dinvdepth is not looked at) and _backward_depth
+// ptgs_splat_gaussians_backward (depth == false: dL_dinvdepth is not looked at), _backward_depth and
+// _backward_pose (pose: dL_dview is written as well; a null or non-device dL_dview is refused before
+// anything is enqueued, and an empty set of Gaussians gives sixteen zeros)
 static int splat_backward_call(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t w, uint32_t h,
                                const float bg[3], const float* dL_dout, bool depth, const float* dL_dinvdepth,
-                               const ptgs_gaussian_grads* grads, void* stream, const char* name) {
+                               const ptgs_gaussian_grads* grads, void* stream, const char* name, bool pose = false,
+                               float* dL_dview = nullptr) {
   if (!c) return PTGS_EINVAL;
   if (!g || !ubo || !bg || !dL_dout || !grads || (depth && !dL_dinvdepth)) return fail(c, PTGS_EINVAL, "null argument");
+  if (pose && !dL_dview) return fail(c, PTGS_EINVAL, "null argument (dL_dview)");
   if (g->ids) return fail(c, PTGS_EINVAL, "the backward pass takes the Gaussians in their original order (ids must be NULL)");
-  if (g->count == 0) return PTGS_OK;  // (empty arrays may be null)
+  if (pose && !is_device_ptr(dL_dview)) return fail(c, PTGS_EINVAL, "dL_dview must be a device pointer");
+  if (g->count == 0) {  // (empty arrays may be null)
+    if (!pose) return PTGS_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return hip_rc(c, splat_pose_finish(nullptr, 0, dL_dview, (hipStream_t)stream), name);
+  }
   if (!g->means || !g->scales || !g->rotations || !g->opacities || !g->colors)
     return fail(c, PTGS_EINVAL, "null gaussian array");
   if (!grads->means || !grads->scales || !grads->rotations || !grads->opacities || !grads->colors)
@@ -1100,11 +1139,14 @@ static int splat_backward_call(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_
                 f.H, g->count, w, h);
   HIPCHK(c, hipSetDevice(c->device));
   float* acc = nullptr;
+  float* partials = nullptr;
   HIPCHK(c, splat_backward_scratch(c->frames.current(), f.n, depth ? GS_BWD_ACC_DEPTH : GS_BWD_ACC, &acc));
+  if (pose) HIPCHK(c, splat_backward_pose_scratch(c->frames.current(), f.n, &partials));
   float mvp[16];
   mat4_mul(ubo->proj, ubo->view, mvp);
   const hipError_t e = splat_gaussians_backward(f, acc, g, ubo->view, mvp, ubo->proj[0], ubo->proj[5], bg, dL_dout,
-                                                depth ? dL_dinvdepth : nullptr, grads, (hipStream_t)stream);
+                                                depth ? dL_dinvdepth : nullptr, grads, (hipStream_t)stream,
+                                                ubo->proj, partials, pose ? dL_dview : nullptr);
   return hip_rc(c, e, name);
 }
 
@@ -1119,6 +1161,13 @@ int ptgs_splat_gaussians_backward_depth(ptgs_ctx* c, const ptgs_gaussians* g, co
                                         const ptgs_gaussian_grads* grads, void* stream) {
   return splat_backward_call(c, g, ubo, w, h, bg, dL_dout, true, dL_dinvdepth, grads, stream,
                              "ptgs_splat_gaussians_backward_depth");
+}
+
+int ptgs_splat_gaussians_backward_pose(ptgs_ctx* c, const ptgs_gaussians* g, const ptgs_ubo* ubo, uint32_t w,
+                                       uint32_t h, const float bg[3], const float* dL_dout, const float* dL_dinvdepth,
+                                       const ptgs_gaussian_grads* grads, float* dL_dview, void* stream) {
+  return splat_backward_call(c, g, ubo, w, h, bg, dL_dout, dL_dinvdepth != nullptr, dL_dinvdepth, grads, stream,
+                             "ptgs_splat_gaussians_backward_pose", true, dL_dview);
 }
 
 int ptgs_splat_gaussians_invdepth(ptgs_ctx* c, uint32_t w, uint32_t h, float* out_invdepth, void* stream) {

@@ -701,6 +701,12 @@ hipError_t splat_backward_scratch(SplatWorkspace* w, uint32_t n, uint32_t floats
   return e;
 }
 
+hipError_t splat_backward_pose_scratch(SplatWorkspace* w, uint32_t n, float** partials) {
+  const hipError_t e = ensure(w->pose_partials, (size_t)((n + 255u) / 256u) * GS_POSE_K * 4);
+  *partials = (float*)w->pose_partials.p;
+  return e;
+}
+
 void splat_get_tile_rows(const SplatWorkspace* w, const unsigned long long** rows, uint32_t* cap) {
   *rows = w->last_scap ? (const unsigned long long*)w->tile_slots.p : nullptr;
   *cap = w->last_scap;

@@ -29,12 +29,18 @@
 //   both backward kernels are templated on DEPTH (ptgs_splat_gaussians_backward_depth): the blend adds
 //   (1 / d) dL/dD to c . dL/dC and a tenth sum, dL/d(1/d); the projection carries that to the mean through d.
 // The DEPTH = false instantiations are the kernels as they were.
+//
+// The camera pose (ptgs_splat_gaussians_backward_pose): the projection backward already forms what dL/d view is
+// made of, per Gaussian; the POSE instantiations sum the twelve shares over the workgroup (DPP, LDS) into one row
+// of partials per workgroup, and gs_pose_finish_kernel, the next launch on the stream, adds the rows in float64
+// in a fixed order. No atomics: given the accumulator, dL/d view is reproducible. DESIGN.md 5h.
 #include <hip/hip_runtime.h>
 
 #include "../../include/ptgs/ptgs.h"
 #include "detmath.h"
 #include "splat_backward.h"
 #include "splat_backward_math.h"
+#include "splat_partial_sum.h"
 
 namespace ptgs {
 
@@ -49,19 +55,6 @@ namespace ptgs {
 #define GB_LN2 0.69314718055994531f
 static_assert(GS_BWD_ACC == 9, "2D mean x2, staged quadratic A B C, log2 opacity, colour x3");
 static_assert(GS_BWD_ACC_DEPTH == GS_BWD_ACC + 1, "and 1 / d");
-
-// Wave64 float sum in DPP (row_shr 1/2/4/8 inside rows of 16, then row_bcast 15 / 31): lane 63 ends with
-// the sum of all 64, returned wave-uniform. Every lane of the wave must be active.
-__device__ __forceinline__ float gb_wave_sum(float v) {
-  auto step = [](float x, int y) { return x + __int_as_float(y); };
-  v = step(v, __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xF, 0xF, false));  // row_shr:1
-  v = step(v, __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x112, 0xF, 0xF, false));  // row_shr:2
-  v = step(v, __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xF, 0xF, false));  // row_shr:4
-  v = step(v, __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xF, 0xF, false));  // row_shr:8
-  v = step(v, __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xA, 0xF, false));  // row_bcast:15
-  v = step(v, __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xC, 0xF, false));  // row_bcast:31
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
 
 // One batch of a tile's list into LDS: work-item tid stages pair base + tid (records, Gaussian ids, quadrant
 // masks). INVD: the free fourth word of the third stage entry holds 1 / d (d: the record's view depth, the
@@ -302,59 +295,112 @@ struct GbOut {
   float *means, *scales, *rots, *opac, *colors, *means2d, *conics;
 };
 
-// DEPTH: the accumulator has the tenth sum, dL/d(1/d), which reaches the mean through d (splat_backward_math.h)
-template <bool DEPTH>
+struct GbProj {
+  float m[16];  // the ubo's proj, column-major (POSE: d ph / d view)
+};
+
+// DEPTH: the accumulator has the tenth sum, dL/d(1/d), which reaches the mean through d (splat_backward_math.h).
+// POSE: the workgroup also leaves the sum of its Gaussians' twelve shares of dL/d view (gs_project_backward_one)
+// in partials[blockIdx.x * GS_POSE_K ..]: over the wave with gb_wave_sum, which needs every lane, so this form
+// keeps the lanes past n (they and the culled Gaussians add zeros), over the four waves through LDS, and one
+// plain store per value. gs_pose_finish_kernel adds the rows. The POSE = false instantiations are the kernels as
+// they were (proj and partials are not read).
+template <bool DEPTH, bool POSE>
 __global__ __launch_bounds__(256) void gs_project_backward_kernel(GbCam cam, const float* __restrict__ means,
                                                                    const float* __restrict__ scales,
                                                                    const float* __restrict__ rots,
                                                                    const float* __restrict__ opac, uint32_t n,
                                                                    const int* __restrict__ radii,
-                                                                   const float* __restrict__ acc, GbOut out) {
+                                                                   const float* __restrict__ acc, GbOut out,
+                                                                   GbProj proj, float* __restrict__ partials) {
   constexpr uint32_t ACC = DEPTH ? GS_BWD_ACC_DEPTH : GS_BWD_ACC;
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const bool visible = radii[i] > 0;  // (a culled Gaussian is in no tile's list: its sums are zero)
-  const float* s9 = acc + (size_t)i * ACC;
-  const float dgx = s9[0], dgy = s9[1];
-  const float da = -0.5f * GB_L2E * s9[2], db = -GB_L2E * s9[3], dc = -0.5f * GB_L2E * s9[4];
-  const float o = opac[i];
-  out.opac[i] = (visible && o > 0.0f) ? s9[5] / (o * GB_LN2) : 0.0f;
-  out.colors[3 * i] = s9[6];
-  out.colors[3 * i + 1] = s9[7];
-  out.colors[3 * i + 2] = s9[8];
-  if (out.means2d) {
-    out.means2d[2 * i] = dgx;
-    out.means2d[2 * i + 1] = dgy;
-  }
-  if (out.conics) {
-    out.conics[3 * i] = da;
-    out.conics[3 * i + 1] = db;
-    out.conics[3 * i + 2] = dc;
-  }
-  float dm[3] = {0.0f, 0.0f, 0.0f}, dsc[3] = {0.0f, 0.0f, 0.0f}, dq[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (visible)
-    gs_project_backward_one<DEPTH>(cam, means + 3 * i, scales + 3 * i, rots + 4 * i, dgx, dgy, da, db, dc, dm, dsc, dq,
-                                   DEPTH ? s9[GS_BWD_ACC] : 0.0f);
+  if (!POSE && i >= n) return;
+  float dv[GS_POSE_K];
+  if (POSE) {
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    out.means[3 * i + k] = dm[k];
-    out.scales[3 * i + k] = dsc[k];
+    for (int k = 0; k < GS_POSE_K; ++k) dv[k] = 0.0f;
   }
+  if (!POSE || i < n) {
+    const bool visible = radii[i] > 0;  // (a culled Gaussian is in no tile's list: its sums are zero)
+    const float* s9 = acc + (size_t)i * ACC;
+    const float dgx = s9[0], dgy = s9[1];
+    const float da = -0.5f * GB_L2E * s9[2], db = -GB_L2E * s9[3], dc = -0.5f * GB_L2E * s9[4];
+    const float o = opac[i];
+    out.opac[i] = (visible && o > 0.0f) ? s9[5] / (o * GB_LN2) : 0.0f;
+    out.colors[3 * i] = s9[6];
+    out.colors[3 * i + 1] = s9[7];
+    out.colors[3 * i + 2] = s9[8];
+    if (out.means2d) {
+      out.means2d[2 * i] = dgx;
+      out.means2d[2 * i + 1] = dgy;
+    }
+    if (out.conics) {
+      out.conics[3 * i] = da;
+      out.conics[3 * i + 1] = db;
+      out.conics[3 * i + 2] = dc;
+    }
+    float dm[3] = {0.0f, 0.0f, 0.0f}, dsc[3] = {0.0f, 0.0f, 0.0f}, dq[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (visible)
+      gs_project_backward_one<DEPTH, POSE>(cam, means + 3 * i, scales + 3 * i, rots + 4 * i, dgx, dgy, da, db, dc, dm,
+                                           dsc, dq, DEPTH ? s9[GS_BWD_ACC] : 0.0f, proj.m, dv);
 #pragma unroll
-  for (int k = 0; k < 4; ++k) out.rots[4 * i + k] = dq[k];
+    for (int k = 0; k < 3; ++k) {
+      out.means[3 * i + k] = dm[k];
+      out.scales[3 * i + k] = dsc[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out.rots[4 * i + k] = dq[k];
+  }
+  if (POSE) {
+    __shared__ float s_pose[4][GS_POSE_K];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+#pragma unroll
+    for (int k = 0; k < GS_POSE_K; ++k) {  // (every lane of the workgroup is here)
+      const float s = gb_wave_sum(dv[k]);
+      if (lane == 63) s_pose[wave][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < GS_POSE_K)
+      partials[(size_t)blockIdx.x * GS_POSE_K + threadIdx.x] =
+          (s_pose[0][threadIdx.x] + s_pose[1][threadIdx.x]) + (s_pose[2][threadIdx.x] + s_pose[3][threadIdx.x]);
+  }
+}
+
+// The second stage of dL/d view: one workgroup adds the `rows` partial rows of this call in float64, in a fixed
+// order (splat_partial_sum.h), and writes the 16 floats column-major like ptgs_ubo.view: entry c * 4 + r =
+// dL/d view[r][c]; row 3 (held at (0, 0, 0, 1)) is exactly 0. rows == 0: sixteen zeros.
+__global__ __launch_bounds__(GS_PSUM_BLOCK) void gs_pose_finish_kernel(const float* __restrict__ partials, uint32_t rows,
+                                                                        float* __restrict__ dview) {
+  __shared__ double s_seg[GS_POSE_K * GS_PSUM_BLOCK];
+  const double sum = gs_sum_partial_rows<GS_POSE_K, GS_PSUM_BLOCK>(partials, rows, s_seg);
+  const uint32_t t = threadIdx.x;
+  if (t < GS_POSE_K) dview[(t & 3u) * 4u + (t >> 2)] = (float)sum;  // partial k = r * 4 + c
+  if (t < 4) dview[t * 4u + 3u] = 0.0f;
+}
+
+template <bool DEPTH, bool POSE>
+static hipError_t gb_launch_project(const SplatFrame& f, const GbCam& cam, const ptgs_gaussians* g, const float* acc,
+                                    const GbOut& out, const GbProj& proj, float* partials, hipStream_t s) {
+  hipLaunchKernelGGL((gs_project_backward_kernel<DEPTH, POSE>), dim3((f.n + 255u) / 256u), dim3(256), 0, s, cam,
+                     g->means, g->scales, g->rotations, g->opacities, f.n, f.radii, acc, out, proj, partials);
+  return hipGetLastError();
 }
 
 hipError_t splat_gaussians_backward(const SplatFrame& f, float* acc, const ptgs_gaussians* g, const float* view,
                                     const float* mvp, float p00, float p11, const float bg[3], const float* dL_dout,
-                                    const float* dL_dinvdepth, const ptgs_gaussian_grads* grads, hipStream_t s) {
+                                    const float* dL_dinvdepth, const ptgs_gaussian_grads* grads, hipStream_t s,
+                                    const float* proj, float* pose_partials, float* dL_dview) {
   const uint32_t n = f.n;
-  const bool depth = dL_dinvdepth != nullptr;
+  const bool depth = dL_dinvdepth != nullptr, pose = dL_dview != nullptr;
   hipError_t e;
   if ((e = hipMemsetAsync(acc, 0, (size_t)n * (depth ? GS_BWD_ACC_DEPTH : GS_BWD_ACC) * 4, s))) return e;
   GbCam cam;
+  GbProj pr = {};
   for (int k = 0; k < 16; ++k) {
     cam.view[k] = view[k];
     cam.mvp[k] = mvp[k];
+    if (pose) pr.m[k] = proj[k];
   }
   cam.fx = p00 * (float)f.W * 0.5f;
   cam.fy = p11 * (float)f.H * 0.5f;
@@ -373,12 +419,18 @@ hipError_t splat_gaussians_backward(const SplatFrame& f, float* acc, const ptgs_
   if ((e = hipGetLastError())) return e;
   const GbOut out = {grads->means, grads->scales, grads->rotations, grads->opacities, grads->colors, grads->means2d,
                      grads->conics};
-  if (depth)
-    hipLaunchKernelGGL(gs_project_backward_kernel<true>, dim3((n + 255u) / 256u), dim3(256), 0, s, cam, g->means,
-                       g->scales, g->rotations, g->opacities, n, f.radii, (const float*)acc, out);
-  else
-    hipLaunchKernelGGL(gs_project_backward_kernel<false>, dim3((n + 255u) / 256u), dim3(256), 0, s, cam, g->means,
-                       g->scales, g->rotations, g->opacities, n, f.radii, (const float*)acc, out);
+  if (!pose)
+    return depth ? gb_launch_project<true, false>(f, cam, g, acc, out, pr, nullptr, s)
+                 : gb_launch_project<false, false>(f, cam, g, acc, out, pr, nullptr, s);
+  // every row the finish reads is written by this call's projection launch: (n + 255) / 256 of them
+  if ((e = depth ? gb_launch_project<true, true>(f, cam, g, acc, out, pr, pose_partials, s)
+                 : gb_launch_project<false, true>(f, cam, g, acc, out, pr, pose_partials, s)))
+    return e;
+  return splat_pose_finish(pose_partials, (n + 255u) / 256u, dL_dview, s);
+}
+
+hipError_t splat_pose_finish(const float* partials, uint32_t rows, float* dL_dview, hipStream_t s) {
+  hipLaunchKernelGGL(gs_pose_finish_kernel, dim3(1), dim3(GS_PSUM_BLOCK), 0, s, partials, rows, dL_dview);
   return hipGetLastError();
 }
 

@@ -31,10 +31,19 @@ struct GbCam {
 // The same case then lands at 7e-6, under float32 autograd's error.
 // DEPTH: dinvd = dL/d(1/d) as well, the inverse depth's share (D = sum wgt / d): it reaches the mean through
 // d = -(V row 2) . (mean, 1) alone, dL/dd = -dinvd / d^2. Order and membership carry no gradient.
-template <bool DEPTH = false>
+// POSE: dview[r * 4 + c], r < 3, c < 4 = this Gaussian's share of dL/d view[r][c] as well (twelve floats, every
+// one written), the same function read as a function of the view: (x, y, -d) = view (mean, 1), W = the view's
+// upper-left 3x3 in T = J W, ph = (proj view)(mean, 1) with proj (column-major float[16]) a constant; fx, fy and
+// the clamp limits are constants, a clamped tx depends on the view through d only, and row 3 of the view is held
+// at (0, 0, 0, 1). With mh = (mean, 1):
+//   dview[r][c] = g_r mh[c],  g = (dpx, dpy, -dd) + the first three entries of proj^T (dphx, dphy, 0, dphw)
+//   dview[r][k] += (J^T dT)[r][k], k < 3: J00 dT[0][k]; J11 dT[1][k]; J02 dT[0][k] + J12 dT[1][k]
+// GbCam stays as it is (its layout is packed by the host tests): proj comes beside it.
+template <bool DEPTH = false, bool POSE = false>
 PTGS_HD void gs_project_backward_one(const GbCam& cam, const float* mean, const float* scale, const float* rot,
                                      float dgx, float dgy, float da, float db, float dc, float* dm, float* dsc,
-                                     float* dq, float dinvd = 0.0f) {
+                                     float* dq, float dinvd = 0.0f, const float* proj = nullptr,
+                                     float* dview = nullptr) {
   // ---- the forward again (gs_preprocess_one) ----
   const float* V = cam.view;  // column-major: row r, col c = V[c*4 + r]
   const float* P = cam.mvp;
@@ -143,6 +152,23 @@ PTGS_HD void gs_project_backward_one(const GbCam& cam, const float* mean, const 
   for (int k = 0; k < 3; ++k)
     dm[k] = ((dpx * Wm[0][k] + dpy * Wm[1][k]) - dd * Wm[2][k]) +
             ((dphx * P[4 * k] + dphy * P[4 * k + 1]) + dphw * P[4 * k + 3]);
+  if (POSE) {
+    const float mh[4] = {mx, my, mz, 1.0f};
+    const float g3[3] = {dpx, dpy, -dd};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      // d ph / d (view (mean, 1))[r] = column r of proj
+      const float gr = g3[r] + ((dphx * proj[4 * r] + dphy * proj[4 * r + 1]) + dphw * proj[4 * r + 3]);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) dview[4 * r + c] = gr * mh[c];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      dview[k] += J00 * dT[0][k];
+      dview[4 + k] += J11 * dT[1][k];
+      dview[8 + k] += J02 * dT[0][k] + J12 * dT[1][k];
+    }
+  }
 }
 
 }  // namespace ptgs

@@ -36,6 +36,7 @@
 // splat_sh_math.h (host / device).
 #include "splat_sh.h"
 
+#include "splat_partial_sum.h"
 #include "splat_sh_math.h"
 
 namespace ptgs {
@@ -141,12 +142,17 @@ __global__ __launch_bounds__(256) void gs_activate_kernel(const float* log_scale
 // reads the row completely first), and the block goes out with lane-contiguous stores. VIN / VOUT: sh / dsh
 // are 16-B aligned. dmeans: NULL (the direction part is skipped), or dL/d(mean) is added to it, each Gaussian
 // by its own work-item: no atomics.
-template <int DEG, bool VIN, bool VOUT>
+// EYE (ptgs_gaussians_sh_colors_backward_eye): the workgroup also leaves the sum of what its Gaussians add to
+// dL/d(mean) (formed with dmeans NULL too) in eye_partials[3 blockIdx.x ..]: over the wave in DPP, over the four
+// waves through LDS, three plain stores; gs_sh_eye_finish_kernel adds the rows and negates. The EYE = false
+// instantiations are the kernels as they were.
+template <int DEG, bool VIN, bool VOUT, bool EYE>
 __global__ __launch_bounds__(SH_WG) void gs_sh_colors_backward_kernel(const float* __restrict__ means,
                                                                      const float* __restrict__ sh, uint32_t count,
                                                                      uint32_t active, v3 cam,
                                                                      const float* __restrict__ dcolors,
-                                                                     float* __restrict__ dsh, float* dmeans) {
+                                                                     float* __restrict__ dsh, float* dmeans,
+                                                                     float* __restrict__ eye_partials) {
   constexpr uint32_t R = sh_row(DEG);  // floats per row
   constexpr uint32_t S = R | 1u;       // LDS row stride
   const uint32_t first = blockIdx.x * (uint32_t)SH_WG, t = threadIdx.x;
@@ -165,13 +171,14 @@ __global__ __launch_bounds__(SH_WG) void gs_sh_colors_backward_kernel(const floa
     __syncthreads();
   }
 #endif
+  float dm[3] = {0.0f, 0.0f, 0.0f};  // (EYE) what this Gaussian adds to dL/d(mean)
   if (t < nrows) {
     const size_t i3 = (size_t)(first + t) * 3;
     float len = 0.0f;
     v3 dir = mk3(0.0f);
     if (DEG > 0 && active > 0) dir = sh_dir(means + i3, cam, &len);  // (the DC band does not see the direction)
     const float dcol[3] = {dcolors[i3], dcolors[i3 + 1], dcolors[i3 + 2]};
-    sh_backward_one<DEG>(row, active, dir, len, dcol, drow, dmeans ? dmeans + i3 : nullptr);
+    sh_backward_one<DEG>(row, active, dir, len, dcol, drow, dmeans ? dmeans + i3 : nullptr, EYE ? dm : nullptr);
   }
 #if !defined(PTGS_SH_ROWWISE)
   if (DEG > 0) {
@@ -179,6 +186,26 @@ __global__ __launch_bounds__(SH_WG) void gs_sh_colors_backward_kernel(const floa
     sh_stage_out<R, S, VOUT>(rows, dst, nrows * R, t);
   }
 #endif
+  if (EYE) {  // (every work-item of the workgroup is here; those past nrows add zeros)
+    __shared__ float s_eye[SH_WG / 64][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float s = gb_wave_sum(dm[k]);
+      if ((t & 63u) == 63u) s_eye[t >> 6][k] = s;
+    }
+    __syncthreads();
+    if (t < 3) eye_partials[(size_t)blockIdx.x * 3 + t] = (s_eye[0][t] + s_eye[1][t]) + (s_eye[2][t] + s_eye[3][t]);
+  }
+}
+
+// The second stage of dL/d(camera_pos): one workgroup adds the `rows` partial rows of this call in float64, in a
+// fixed order (splat_partial_sum.h); the eye moves against the means, hence the sign.
+__global__ __launch_bounds__(GS_PSUM_BLOCK_EYE) void gs_sh_eye_finish_kernel(const float* __restrict__ partials,
+                                                                              uint32_t rows,
+                                                                              float* __restrict__ deye) {
+  __shared__ double s_seg[3 * GS_PSUM_BLOCK_EYE];
+  const double sum = gs_sum_partial_rows<3, GS_PSUM_BLOCK_EYE>(partials, rows, s_seg);
+  if (threadIdx.x < 3) deye[threadIdx.x] = (float)(-sum);
 }
 
 // no __restrict__: an output may be its upstream gradient (in place)
@@ -216,13 +243,13 @@ hipError_t launch_sh(const float* means, const float* sh, uint32_t count, uint32
   return hipGetLastError();
 }
 
-template <int DEG>
+template <int DEG, bool EYE>
 hipError_t launch_sh_backward(const float* means, const float* sh, uint32_t count, uint32_t active, v3 cam,
-                              const float* dcolors, float* dsh, float* dmeans, hipStream_t s) {
+                              const float* dcolors, float* dsh, float* dmeans, float* eye_partials, hipStream_t s) {
   const uint32_t blocks = (uint32_t)(((uint64_t)count + SH_WG - 1) / SH_WG);
-#define PTGS_SH_BWD(VIN, VOUT)                                                                        \
-  gs_sh_colors_backward_kernel<DEG, VIN, VOUT><<<blocks, SH_WG, 0, s>>>(means, sh, count, active, cam, dcolors, \
-                                                                        dsh, dmeans)
+#define PTGS_SH_BWD(VIN, VOUT)                                                                                  \
+  gs_sh_colors_backward_kernel<DEG, VIN, VOUT, EYE><<<blocks, SH_WG, 0, s>>>(means, sh, count, active, cam, dcolors, \
+                                                                             dsh, dmeans, eye_partials)
   const bool vin = ((uintptr_t)sh & 15u) == 0, vout = ((uintptr_t)dsh & 15u) == 0;
   if constexpr (DEG == 0) {  // (degree 0 stages nothing)
     PTGS_SH_BWD(false, false);
@@ -261,12 +288,32 @@ hipError_t splat_sh_colors_backward(const float* means, const float* sh, uint32_
   const v3 c = mk3(cam[0], cam[1], cam[2]);
   if (sh_degree == 0 || active_degree == 0) dmeans = nullptr;  // no direction part: neither read nor written
   switch (sh_degree) {
-    case 0: return launch_sh_backward<0>(means, sh, count, active_degree, c, dcolors, dsh, dmeans, s);
-    case 1: return launch_sh_backward<1>(means, sh, count, active_degree, c, dcolors, dsh, dmeans, s);
-    case 2: return launch_sh_backward<2>(means, sh, count, active_degree, c, dcolors, dsh, dmeans, s);
-    case 3: return launch_sh_backward<3>(means, sh, count, active_degree, c, dcolors, dsh, dmeans, s);
+    case 0: return launch_sh_backward<0, false>(means, sh, count, active_degree, c, dcolors, dsh, dmeans, nullptr, s);
+    case 1: return launch_sh_backward<1, false>(means, sh, count, active_degree, c, dcolors, dsh, dmeans, nullptr, s);
+    case 2: return launch_sh_backward<2, false>(means, sh, count, active_degree, c, dcolors, dsh, dmeans, nullptr, s);
+    case 3: return launch_sh_backward<3, false>(means, sh, count, active_degree, c, dcolors, dsh, dmeans, nullptr, s);
   }
   return hipErrorInvalidValue;
+}
+
+hipError_t splat_sh_colors_backward_eye(const float* means, const float* sh, uint32_t count, uint32_t sh_degree,
+                                        uint32_t active_degree, const float cam[3], const float* dcolors, float* dsh,
+                                        float* dmeans, float* eye_partials, float* deye, hipStream_t s) {
+  if (sh_degree > 3) return hipErrorInvalidValue;
+  if (count == 0 || sh_degree == 0 || active_degree == 0) {  // no direction part: the eye gets exact zeros
+    const hipError_t e = hipMemsetAsync(deye, 0, 3 * sizeof(float), s);
+    return e ? e : splat_sh_colors_backward(means, sh, count, sh_degree, active_degree, cam, dcolors, dsh, dmeans, s);
+  }
+  const v3 c = mk3(cam[0], cam[1], cam[2]);
+  const uint32_t act = active_degree;
+  hipError_t e = hipErrorInvalidValue;
+  if (sh_degree == 1) e = launch_sh_backward<1, true>(means, sh, count, act, c, dcolors, dsh, dmeans, eye_partials, s);
+  if (sh_degree == 2) e = launch_sh_backward<2, true>(means, sh, count, act, c, dcolors, dsh, dmeans, eye_partials, s);
+  if (sh_degree == 3) e = launch_sh_backward<3, true>(means, sh, count, act, c, dcolors, dsh, dmeans, eye_partials, s);
+  if (e) return e;
+  // every row the finish reads was written by the launch above
+  gs_sh_eye_finish_kernel<<<1, GS_PSUM_BLOCK_EYE, 0, s>>>(eye_partials, splat_sh_eye_rows(count), deye);
+  return hipGetLastError();
 }
 
 hipError_t splat_sh_activate(const float* log_scales, const float* logits, uint32_t count, float* scales,

@@ -146,20 +146,30 @@ PTGS_HD v3 sh_dir_grad(const float* row, uint32_t active, v3 dir, const float* d
 //   dres[c] = (res + 0.5 < 0) ? 0 : dcol[c]      (the forward's own test, recomputed with its arithmetic)
 //   drow[k][c] = f_k * dres[c]                   (one multiply; bands above `active`: 0)
 //   dmean += (v - dir (dir . v)) / len           (v: sh_dir_grad; nothing is added at len == 0)
+// dm_out: NULL, or 3 floats that receive that same (v - dir (dir . v)) / len, zeros where nothing is added: the
+// Gaussian's share of -dL/d(camera_pos) (the colour sees mean - camera_pos alone); it is formed with dmean NULL too.
 template <int DEG>
 PTGS_HD void sh_backward_one(const float* row, uint32_t active, v3 dir, float len, const float* dcol, float* drow,
-                             float* dmean) {
+                             float* dmean, float* dm_out = nullptr) {
   float r[3], dres[3];
   sh_res<DEG>(row, active, dir, r);
 #pragma unroll
   for (int c = 0; c < 3; ++c) dres[c] = r[c] < 0.0f ? 0.0f : dcol[c];
-  if (DEG >= 1 && dmean && active >= 1 && len > 0.0f) {
+  if (dm_out) dm_out[0] = dm_out[1] = dm_out[2] = 0.0f;
+  if (DEG >= 1 && (dmean || dm_out) && active >= 1 && len > 0.0f) {
     const v3 v = sh_dir_grad<DEG>(row, active, dir, dres);
     const float dv = dot3(dir, v);
     const v3 dm = (v - dir * dv) / len;
-    dmean[0] = dmean[0] + dm.x;
-    dmean[1] = dmean[1] + dm.y;
-    dmean[2] = dmean[2] + dm.z;
+    if (dmean) {
+      dmean[0] = dmean[0] + dm.x;
+      dmean[1] = dmean[1] + dm.y;
+      dmean[2] = dmean[2] + dm.z;
+    }
+    if (dm_out) {
+      dm_out[0] = dm.x;
+      dm_out[1] = dm.y;
+      dm_out[2] = dm.z;
+    }
   }
   float f[(DEG + 1) * (DEG + 1)];
   sh_factors<DEG>(active, dir, f);

@@ -20,6 +20,7 @@ struct SplatWorkspace {
   DevBuf fsq;                 // the fused front end's slice queue
   DevBuf cskip;               // per 256-Gaussian chunk: skipped by a tile-row-restricted frame
   DevBuf grad_acc;            // the backward pass's per-Gaussian sums (splat_backward.hip)
+  DevBuf pose_partials;       // the pose gradient's per-workgroup partial sums (splat_backward.hip)
   DevBuf under_copy;          // a stats frame's `under` where it overlaps `out` (gs_plan_under_copy)
   uint32_t sp_cap = 0;        // spill pool capacity (pairs)
   uint32_t incomplete = 0;    // frames reported incomplete (spill pool exhausted) since the last status clear

@@ -287,14 +287,17 @@ class Renderer:
 
     def splat_gaussians_backward(self, g: dict, ubo: Ubo, width: int, height: int, dL_dout, bg=(0.0, 0.0, 0.0),
                                  want_means2d: bool = False, want_conics: bool = False, stream=None,
-                                 dL_dinvdepth=None) -> dict:
+                                 dL_dinvdepth=None, want_view: bool = False) -> dict:
         """ptgs_splat_gaussians_backward: the gradients of the latest frame, which must be a full-frame
         splat_gaussians(g, ubo, width, height, ..., bg, want_stats=True) of a renderer that publishes
         (FLAG_SPLAT_PUBLISH). dL_dout: float32 [H, W, 4]. Returns new tensors "means", "scales" (linear),
         "rotations" (un-normalised), "opacities", "colors" and, when asked for, "means2d" (dL/d pixel
         position) and "conics" (dL/d conic a, b, c). Stream-ordered; not bit-reproducible (float atomics).
         dL_dinvdepth: float32 [H, W], the gradient with respect to splat_gaussians_invdepth's output; with it the
-        call is ptgs_splat_gaussians_backward_depth (the gradients of a loss on both, in one pass)."""
+        call is ptgs_splat_gaussians_backward_depth (the gradients of a loss on both, in one pass).
+        want_view: the call is ptgs_splat_gaussians_backward_pose (with or without dL_dinvdepth) and the result
+        gains "view", a float32 device tensor [4, 4] with G[r][c] = dL/d view[r][c] in math indexing (the
+        transpose of the call's column-major 16 floats); row 3 is exactly 0."""
         import torch
         n = int(g["means"].shape[0])
         self._f32(("means", g["means"], n * 3), ("scales", g["scales"], n * 3), ("rotations", g["rotations"], n * 4),
@@ -312,6 +315,15 @@ class Renderer:
         for k, t in out.items():
             setattr(gr, k, _ptr(t))
         bgc = np.asarray(bg, np.float32)
+        if want_view:
+            raw = torch.empty(16, dtype=torch.float32, device=dev)
+            rc = self.lib.ptgs_splat_gaussians_backward_pose(self._h, C.byref(_gaussians(g)), C.byref(ubo), width,
+                                                             height, _abi.fptr(bgc), _ptr(dL_dout),
+                                                             _ptr(dL_dinvdepth) or None, C.byref(gr), _ptr(raw),
+                                                             _stream(stream))
+            self._chk(rc, "ptgs_splat_gaussians_backward_pose")
+            out["view"] = raw.view(4, 4).t()
+            return out
         if dL_dinvdepth is not None:
             rc = self.lib.ptgs_splat_gaussians_backward_depth(self._h, C.byref(_gaussians(g)), C.byref(ubo), width,
                                                               height, _abi.fptr(bgc), _ptr(dL_dout),
@@ -411,12 +423,14 @@ class Renderer:
         return sc, op
 
     def sh_colors_backward(self, means, sh, camera_pos, dL_dcolors, active_degree=None, dL_dmeans=None, stream=None,
-                           want_means: bool = True):
+                           want_means: bool = True, want_eye: bool = False):
         """ptgs_gaussians_sh_colors_backward: (dL_dsh, dL_dmeans) of sh_colors(means, sh, camera_pos,
         active_degree=...) given dL_dcolors [N, 3]. dL_dsh is a new tensor shaped like sh; the colour's
         dependence on the means (through the view direction) is ADDED to dL_dmeans [N, 3] (a zero tensor is
         allocated when None) and that tensor is returned: pass the "means" of splat_gaussians_backward.
         want_means=False skips that part (NULL at the C level) and returns (dL_dsh, None).
+        want_eye=True: the call is ptgs_gaussians_sh_colors_backward_eye and the result is (dL_dsh, dL_dmeans,
+        dL_deye), dL_deye a float32 device tensor [3]: the gradient with respect to camera_pos.
         Stream-ordered; reproducible from run to run (no atomics)."""
         import torch
         d = self._sh_degree(sh)
@@ -429,6 +443,15 @@ class Renderer:
                   *([("dL_dmeans", dL_dmeans, n * 3)] if want_means else []))
         dL_dsh = torch.empty((n, (d + 1) ** 2, 3), dtype=torch.float32, device=means.device)
         cam = np.ascontiguousarray(np.asarray(camera_pos, np.float32).reshape(3))
+        if want_eye:
+            dL_deye = torch.empty(3, dtype=torch.float32, device=means.device)
+            rc = self.lib.ptgs_gaussians_sh_colors_backward_eye(self._h, _ptr(means), _ptr(sh), n, d,
+                                                                d if active_degree is None else int(active_degree),
+                                                                _abi.fptr(cam), _ptr(dL_dcolors), _ptr(dL_dsh),
+                                                                _ptr(dL_dmeans) if want_means else None,
+                                                                _ptr(dL_deye), _stream(stream))
+            self._chk(rc, "ptgs_gaussians_sh_colors_backward_eye")
+            return dL_dsh, dL_dmeans, dL_deye
         rc = self.lib.ptgs_gaussians_sh_colors_backward(self._h, _ptr(means), _ptr(sh), n, d,
                                                         d if active_degree is None else int(active_degree),
                                                         _abi.fptr(cam), _ptr(dL_dcolors), _ptr(dL_dsh),
