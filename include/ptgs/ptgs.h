@@ -44,8 +44,9 @@ extern "C" {
                              * ptgs_gaussians_opacity_reset (with the structs ptgs_adam_rows and
                              * ptgs_adam_params), ptgs_splat_gaussians_invdepth,
                              * ptgs_splat_gaussians_backward_depth, ptgs_image_loss_invdepth_l1,
-                             * ptgs_splat_gaussians_backward_pose, ptgs_gaussians_sh_colors_backward_eye;
-                             * ptgs_read_gaussian_ply in ptgs_host.h */
+                             * ptgs_splat_gaussians_backward_pose, ptgs_gaussians_sh_colors_backward_eye,
+                             * ptgs_gaussians_checkpoint_init, ptgs_image_mse; ptgs_read_gaussian_ply and
+                             * ptgs_write_gaussian_ply in ptgs_host.h */
 
 /* ---------------- error codes ---------------- */
 #define PTGS_OK 0
@@ -1001,6 +1002,42 @@ int ptgs_gaussians_adam_step(ptgs_ctx* ctx, uint32_t n, const ptgs_adam_rows* ro
                              void* hip_stream);
 int ptgs_gaussians_opacity_reset(ptgs_ctx* ctx, float* opacity_logits, uint32_t n, float max_opacity,
                                  float* exp_avg /* NULL or n */, float* exp_avg_sq /* NULL or n */, void* hip_stream);
+
+/* The two ends of a training run (pathtracer_gaussiansplatting_amd/train.py): the leaves of a checkpoint from
+ * initialised Gaussians, and the squared error its evaluation reports as PSNR. Both are stream-ordered, wait for
+ * nothing on the host, allocate nothing, use no atomics (two runs give the same bits) and take device pointers.
+ *
+ * ptgs_gaussians_checkpoint_init: the inverse of ptgs_gaussians_activate plus the trainer's RGB2SH, in one launch:
+ * what ptgs_gaussians_from_points wrote (scales 3n, opacities n, colors 3n, post-activation) becomes what a
+ * trainer optimises and ptgs_read_gaussian_ply returns. Numerical contract (f32, no FMA, checkable bit for bit):
+ *   log_scales[e]     = log2x(scales[e]) * 0.69314718055994531f                       (detmath.h log2x)
+ *   opacity_logits[i] = (log2x(o) - log2x(1.0f - o)) * 0.69314718055994531f,   o = opacities[i]
+ *   sh[i][0][c]       = (colors[3 i + c] - 0.5f) / C0f      (IEEE division; C0 of ptgs_gaussians_sh_colors)
+ *   sh[i][k][c]       = +0.0f for every k >= 1
+ * sh: float[n][(sh_degree+1)^2][3], the layout of ptgs_gaussians_sh_colors; sh_degree in 0..3. log2x is an atanh
+ * series, accurate to about 1e-7 relative in the logarithm's value away from 1 and to about 1e-7 absolute near it.
+ * In place is allowed as for activate (log_scales == scales, opacity_logits == opacities); any other overlap of
+ * an output with another array of the call is refused. log2x returns -1e30 for an argument that is not positive,
+ * so o == 0 gives a logit of about -6.9e29 and o == 1 about +6.9e29 (finite, never NaN or Inf; activate maps
+ * them back to less than 1e-38 and to exactly 1), a scale of 0 a log-scale of about -6.9e29: a caller that wants bounded leaves clips its opacities
+ * and scales first. PTGS_EINVAL (message in ptgs_last_error, nothing enqueued): a null ctx; sh_degree above 3; a
+ * null pointer; such an overlap; an output that is not a device pointer. n == 0: PTGS_OK before any pointer is
+ * looked at, nothing is launched.
+ *
+ * ptgs_image_mse: out_sum (device double[1]) = sum over every pixel p and c = 0..2 of (double)(d * d),
+ * d = image_rgba32f[4 p + c] - target[target_channels p + c] in f32 (the product rounded to f32, then widened).
+ * target_channels is 3 or 4, as for ptgs_image_loss_l1_dssim. The sum has a fixed order: at most 1024 workgroups,
+ * each over a contiguous span of pixels (a work-item adds its pixels in index order, the workgroup's 256 sums meet
+ * in a halving tree), then one workgroup adds the workgroups' sums likewise, all in f64. Identical images give
+ * exactly 0. The host computes mse = sum / (3 W H) and PSNR = -10 log10(mse) after reading the double back. The
+ * workgroups' sums (8 KiB) belong to the context since ptgs_create, so the calls of one context must be ordered on
+ * their streams. PTGS_EINVAL: a null ctx; target_channels not 3 or 4; a null image, target or out_sum; out_sum not
+ * a device pointer. width * height == 0: PTGS_OK before any pointer is looked at; out_sum is not written. */
+int ptgs_gaussians_checkpoint_init(ptgs_ctx* ctx, const float* scales, const float* opacities, const float* colors,
+                                   uint32_t n, uint32_t sh_degree, float* log_scales, float* opacity_logits,
+                                   float* sh, void* hip_stream);
+int ptgs_image_mse(ptgs_ctx* ctx, const float* image_rgba32f, const float* target, uint32_t target_channels,
+                   uint32_t width, uint32_t height, double* out_sum, void* hip_stream);
 
 /* Report of the stream-ordered splat (no stats): waits for hip_stream and the context's view streams,
  * then returns (and clears) the counts since the last query. frames / views[v]: frames left

@@ -179,6 +179,17 @@ int ptgs_builder_load_scene_json(ptgs_scene_builder* b, const char* path, const 
 int ptgs_read_gaussian_ply(const char* path, float* means, float* log_scales, float* rotations,
                            float* opacity_logits, float* sh, uint32_t capacity,
                            uint32_t* count, uint32_t* sh_degree);
+/* The inverse of ptgs_read_gaussian_ply: host arrays in its layouts (means 3N, log_scales 3N, rotations 4N w x y z,
+ * opacity_logits N, sh N * (d+1)^2 * 3 as [i][k][c]; values as a trainer holds them, not activated) to a
+ * binary_little_endian file whose float properties are, in the order of the reference trainer's save_ply
+ * (scene/gaussian_model.py construct_list_of_attributes): x y z nx ny nz (the normals written as 0), f_dc_0..2,
+ * f_rest_0..(3((d+1)^2-1)-1) channel-major as the reader documents, opacity, scale_0..2, rot_0..3. Reading the
+ * file back returns every float bit for bit (infinities, -0 and quiet NaNs with their payload included; the
+ * reader widens through double, which quiets a signalling NaN). count == 0 writes the header
+ * alone, and the arrays may then be NULL. PTGS_EINVAL: a null path, sh_degree above 3, a null array with
+ * count > 0; PTGS_EIO: the file cannot be created or written. */
+int ptgs_write_gaussian_ply(const char* path, const float* means, const float* log_scales, const float* rotations,
+                            const float* opacity_logits, const float* sh, uint32_t count, uint32_t sh_degree);
 
 #ifdef __cplusplus
 }

@@ -289,6 +289,8 @@ SYMBOLS = {
     "ptgs_image_loss_invdepth_l1": (_I, [_P, _P, _P, _U, _U, C.c_float, C.c_float, _P, _P, _P]),
     "ptgs_gaussians_adam_step": (_I, [_P, _U, C.POINTER(AdamRows), _U, C.POINTER(AdamParams), _P, _P]),
     "ptgs_gaussians_opacity_reset": (_I, [_P, _P, _U, C.c_float, _P, _P, _P]),
+    "ptgs_gaussians_checkpoint_init": (_I, [_P, _P, _P, _P, _U, _U, _P, _P, _P, _P]),
+    "ptgs_image_mse": (_I, [_P, _P, _P, _U, _U, _U, _P, _P]),
     "ptgs_trace_depth_rows": (_I, [_P, C.POINTER(Ubo), _U, _U, _U, _U, _P, _P]),
     "ptgs_knn3_mean_dist2": (_I, [_P, _P, _U, _P, _P]),
     "ptgs_gaussians_from_points": (_I, [_P, _P, _P, _U, _P, _P, _P, _P, _P, _P]),
@@ -327,6 +329,7 @@ SYMBOLS = {
     "ptgs_image_decode_rgba8": (_I, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(_U), C.POINTER(_U), C.POINTER(_U)]),
     "ptgs_read_ply": (_I, [C.c_char_p, _P, _P, _P, _U, C.POINTER(_U)]),
     "ptgs_read_gaussian_ply": (_I, [C.c_char_p, _P, _P, _P, _P, _P, _U, C.POINTER(_U), C.POINTER(_U)]),
+    "ptgs_write_gaussian_ply": (_I, [C.c_char_p, _P, _P, _P, _P, _P, _U, _U]),
     "ptgs_generate_samples": (_I, [_I, _U, _P, _U, _P, _U, _U, _I, _P]),
     "ptgs_sort_samples": (_I, [_P, _U]),
     "ptgs_morton2d": (_U, [C.c_float, C.c_float]),

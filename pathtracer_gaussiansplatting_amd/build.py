@@ -21,7 +21,7 @@ BUILD = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libptgs.so")
 
 SOURCES = ["api.cpp", "bvh.cpp", "bvh_opt.cpp", "bvh_gpu.hip", "bvh_sah_gpu.hip", "bvh_collapse_gpu.hip", "capture.cpp", "capture_io.cpp", "comm.cpp", "jpeg.cpp", "scene.cpp", "textures.cpp",
-           "pt_kernels.hip", "pt_wavefront.hip", "raster.hip", "splat.hip", "splat_backward.hip", "splat_sh.hip", "splat_densify.hip", "splat_loss.hip", "splat_adam.hip", "knn.hip", "gltf.cpp", "image_decode.cpp", "ply.cpp", "sampling.cpp"]
+           "pt_kernels.hip", "pt_wavefront.hip", "raster.hip", "splat.hip", "splat_backward.hip", "splat_sh.hip", "splat_densify.hip", "splat_loss.hip", "splat_adam.hip", "splat_train.hip", "knn.hip", "gltf.cpp", "image_decode.cpp", "ply.cpp", "sampling.cpp"]
 # pure host code (scene ingest, the traversal tree's optimiser): plain g++, no device pass
 HOST_SOURCES = {"bvh_opt.cpp", "gltf.cpp", "image_decode.cpp", "ply.cpp", "sampling.cpp", "capture_io.cpp", "jpeg.cpp"}
 # per-source extra flags. pt_kernels.hip: SimplifyCFG's common-store sinking merges stores to

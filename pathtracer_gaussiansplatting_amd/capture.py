@@ -92,6 +92,26 @@ def load_gaussian_ply(path: str, lib=None) -> dict:
     return g
 
 
+def save_gaussian_ply(path: str, g: dict, lib=None):
+    """The inverse of load_gaussian_ply (ptgs_write_gaussian_ply): the five arrays of a checkpoint as a trainer
+    holds them (means, log_scales, rotations, opacity_logits, sh [N, (d+1)^2, 3]; numpy arrays or tensors, device
+    tensors are copied to the host) to a binary little-endian point_cloud.ply in the reference trainer's property
+    order. Reading it back gives every float bit for bit."""
+    def host(v, shape):
+        if hasattr(v, "detach"):
+            v = v.detach().cpu().numpy()
+        return np.ascontiguousarray(v, np.float32).reshape(shape)
+
+    n = int(g["means"].shape[0])
+    k = int(g["sh"].shape[1]) if len(g["sh"].shape) == 3 else 0
+    if k not in (1, 4, 9, 16) or int(g["sh"].shape[2]) != 3:
+        raise _abi.PtgsError(f"sh must be [N, (d+1)^2, 3] with d in 0..3 (got {tuple(g['sh'].shape)})")
+    a = [host(g["means"], (n, 3)), host(g["log_scales"], (n, 3)), host(g["rotations"], (n, 4)),
+         host(g["opacity_logits"], (n,)), host(g["sh"], (n, k, 3))]
+    rc = _lib(lib).ptgs_write_gaussian_ply(path.encode(), *[x.ctypes.data for x in a], n, (1, 4, 9, 16).index(k))
+    _abi.check(rc, "ptgs_write_gaussian_ply", f"({path})")
+
+
 def write_jpeg(path: str, pixels: np.ndarray, quality: int = 90, lib=None):
     p = np.ascontiguousarray(pixels, np.uint8)
     comp = 1 if p.ndim == 2 else p.shape[2]

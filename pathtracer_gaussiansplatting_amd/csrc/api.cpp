@@ -43,6 +43,7 @@
 #include "splat_frames.h"
 #include "splat_loss.h"
 #include "splat_sh.h"
+#include "splat_train.h"
 #include "textures.h"
 
 using namespace ptgs;
@@ -65,6 +66,7 @@ struct ptgs_ctx {
   DensifyWorkspace* densify = nullptr;  // the densification plan (ptgs_gaussians_densify_plan / _apply)
   LossWorkspace* loss = nullptr;  // the partial maps and sums of ptgs_image_loss_l1_dssim
   ptgs::DevBuf sh_eye_partials;  // per-workgroup partial sums of ptgs_gaussians_sh_colors_backward_eye
+  ptgs::DevBuf mse_partials;  // per-workgroup sums of ptgs_image_mse: a fixed TRAIN_MSE_MAX_WG doubles, from ptgs_create
   ptgs::WfWorkspace wf;  // wavefront path tracer buffers (PTGS_FLAG_PT_WAVEFRONT)
   ptgs::PtSched pt_sched;  // megakernel tile schedule (heavy tiles first)
   void* comm = nullptr;  // RCCL communicator (ptgs_comm_create)
@@ -423,6 +425,10 @@ int ptgs_create(int hip_device, ptgs_ctx** out) {
   if (hipMemset(c->counters, 0, 8 * sizeof(unsigned long long)) != hipSuccess) { delete c; return PTGS_EHIP; }
   c->densify = densify_workspace_create();
   c->loss = loss_workspace_create();
+  if (c->mse_partials.ensure(TRAIN_MSE_MAX_WG * sizeof(double), 0) != hipSuccess) {
+    ptgs_destroy(c);
+    return PTGS_EHIP;
+  }
   *out = c;
   return PTGS_OK;
 }
@@ -1395,6 +1401,48 @@ int ptgs_gaussians_opacity_reset(ptgs_ctx* c, float* logits, uint32_t n, float m
   HIPCHK(c, hipSetDevice(c->device));
   const hipError_t e = opacity_reset(logits, n, adam_reset_cap(max_opacity), exp_avg, exp_avg_sq, (hipStream_t)stream);
   return hip_rc(c, e, "ptgs_gaussians_opacity_reset");
+}
+
+int ptgs_gaussians_checkpoint_init(ptgs_ctx* c, const float* scales, const float* opacities, const float* colors,
+                                   uint32_t n, uint32_t sh_degree, float* log_scales, float* opacity_logits, float* sh,
+                                   void* stream) {
+  if (!c) return PTGS_EINVAL;
+  if (sh_degree > 3) return fail(c, PTGS_EINVAL, "sh_degree %u above 3", sh_degree);
+  if (n == 0) return PTGS_OK;  // (empty arrays may be null)
+  if (!scales || !opacities || !colors || !log_scales || !opacity_logits || !sh)
+    return fail(c, PTGS_EINVAL, "null argument");
+  // log_scales / opacity_logits may be their own inputs; every other pair of a written array and another array is apart
+  const size_t f = sizeof(float), row = 3u * (sh_degree + 1u) * (sh_degree + 1u);
+  Span sp[6] = {{(const char*)log_scales, (size_t)n * 3 * f, true}, {(const char*)opacity_logits, (size_t)n * f, true},
+                {(const char*)sh, (size_t)n * row * f, true},       {(const char*)scales, (size_t)n * 3 * f, false},
+                {(const char*)opacities, (size_t)n * f, false},     {(const char*)colors, (size_t)n * 3 * f, false}};
+  for (uint32_t i = 0; i < 3; ++i) {
+    for (uint32_t j = 0; j < 6; ++j) {
+      if (j == i || (i < 2 && j == i + 3 && sp[j].p == sp[i].p)) continue;  // (sh's rows are not colors' rows)
+      if (sp[i].p < sp[j].p + sp[j].bytes && sp[j].p < sp[i].p + sp[i].bytes)
+        return fail(c, PTGS_EINVAL, "an output overlaps another array (in place: log_scales == scales, "
+                                    "opacity_logits == opacities)");
+    }
+    if (!is_device_ptr(sp[i].p)) return fail(c, PTGS_EINVAL, "an output is not a device pointer");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipError_t e = train_checkpoint_init(scales, opacities, colors, n, sh_degree, log_scales, opacity_logits, sh,
+                                             (hipStream_t)stream);
+  return hip_rc(c, e, "ptgs_gaussians_checkpoint_init");
+}
+
+int ptgs_image_mse(ptgs_ctx* c, const float* image, const float* target, uint32_t target_channels, uint32_t w,
+                   uint32_t h, double* out_sum, void* stream) {
+  if (!c) return PTGS_EINVAL;
+  if (target_channels != 3 && target_channels != 4)
+    return fail(c, PTGS_EINVAL, "target_channels %u: 3 or 4", target_channels);
+  if ((uint64_t)w * h == 0) return PTGS_OK;  // (an empty image may be null; out_sum is not written)
+  if (!image || !target || !out_sum) return fail(c, PTGS_EINVAL, "null argument");
+  if (!is_device_ptr(out_sum)) return fail(c, PTGS_EINVAL, "out_sum is not a device pointer");
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipError_t e = train_image_mse(image, target, target_channels, (uint64_t)w * h, c->mse_partials.as<double>(),
+                                       out_sum, (hipStream_t)stream);
+  return hip_rc(c, e, "ptgs_image_mse");
 }
 
 int ptgs_splat_status_read(ptgs_ctx* c, ptgs_splat_status* out, void* stream) {

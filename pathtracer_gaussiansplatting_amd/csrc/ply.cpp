@@ -6,7 +6,8 @@
 // term f_dc_0..2 (0.5 + C0 * f_dc, clamped). Elements before "vertex" must have fixed-size rows in
 // binary files (list properties are only skippable in ASCII).
 // ptgs_read_gaussian_ply reads the whole of such a trained-3DGS file (means, log-scales, rotations,
-// opacity logits, SH coefficients) through the same header and row parsing.
+// opacity logits, SH coefficients) through the same header and row parsing; ptgs_write_gaussian_ply, at the
+// end, writes one (binary little endian, the trainer's property order).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -327,4 +328,50 @@ extern "C" int ptgs_read_gaussian_ply(const char* path, float* means, float* log
       }
     }
   });
+}
+
+// The writer of such a checkpoint: see ptgs_host.h. A Gaussian's row is 14 + 3 (d+1)^2 floats, written through one
+// buffer per 4096 rows; every float goes out as its four bytes, least significant first.
+extern "C" int ptgs_write_gaussian_ply(const char* path, const float* means, const float* log_scales,
+                                       const float* rotations, const float* opacity_logits, const float* sh,
+                                       uint32_t count, uint32_t sh_degree) {
+  if (!path || sh_degree > 3) return PTGS_EINVAL;
+  if (count && (!means || !log_scales || !rotations || !opacity_logits || !sh)) return PTGS_EINVAL;
+  const size_t K = (size_t)(sh_degree + 1) * (sh_degree + 1), n_rest = 3 * (K - 1);
+  std::string hdr = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(count) + "\n";
+  auto prop = [&](const std::string& name) { hdr += "property float " + name + "\n"; };
+  for (const char* nm : {"x", "y", "z", "nx", "ny", "nz", "f_dc_0", "f_dc_1", "f_dc_2"}) prop(nm);
+  for (size_t j = 0; j < n_rest; ++j) prop("f_rest_" + std::to_string(j));
+  prop("opacity");
+  for (int a = 0; a < 3; ++a) prop("scale_" + std::to_string(a));
+  for (int a = 0; a < 4; ++a) prop("rot_" + std::to_string(a));
+  hdr += "end_header\n";
+  FILE* f = std::fopen(path, "wb");
+  if (!f) return PTGS_EIO;
+  bool ok = std::fwrite(hdr.data(), 1, hdr.size(), f) == hdr.size();
+  const size_t row_floats = 14 + 3 * K, chunk = 4096;
+  std::vector<uint8_t> buf;
+  buf.reserve(chunk * row_floats * 4);
+  auto put = [&](float v) {
+    uint32_t u;
+    memcpy(&u, &v, 4);
+    for (int b = 0; b < 4; ++b) buf.push_back((uint8_t)(u >> (8 * b)));
+  };
+  for (size_t i0 = 0; i0 < count && ok; i0 += chunk) {
+    buf.clear();
+    const size_t i1 = std::min<size_t>(count, i0 + chunk);
+    for (size_t i = i0; i < i1; ++i) {
+      const float* s = sh + i * K * 3;
+      for (int a = 0; a < 3; ++a) put(means[3 * i + a]);
+      for (int a = 0; a < 3; ++a) put(0.0f);  // nx ny nz
+      for (int c = 0; c < 3; ++c) put(s[c]);
+      for (int c = 0; c < 3; ++c)  // f_rest is channel-major: f_rest[c (K - 1) + (k - 1)] = sh[i][k][c]
+        for (size_t k = 1; k < K; ++k) put(s[k * 3 + c]);
+      put(opacity_logits[i]);
+      for (int a = 0; a < 3; ++a) put(log_scales[3 * i + a]);
+      for (int a = 0; a < 4; ++a) put(rotations[4 * i + a]);
+    }
+    ok = std::fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+  }
+  return (std::fclose(f) == 0 && ok) ? PTGS_OK : PTGS_EIO;
 }

@@ -659,6 +659,49 @@ class Renderer:
                                                    _ptr(exp_avg) or None, _ptr(exp_avg_sq) or None, _stream(stream))
         self._chk(rc, "ptgs_gaussians_opacity_reset")
 
+    # ---------------------------------------------------------------- the ends of a training run
+    def checkpoint_init(self, scales, opacities, colors, sh_degree: int, out=None, stream=None):
+        """ptgs_gaussians_checkpoint_init: (log_scales, opacity_logits, sh) of gaussians_from_points' activated
+        scales [N, 3], opacities [N] and RGB colors [N, 3]: the logarithm, the logit and RGB2SH into the DC
+        term of zeroed sh [N, (sh_degree+1)^2, 3], in one launch. New tensors, or out=(log_scales,
+        opacity_logits, sh) (the first two may be scales / opacities themselves: in place). Stream-ordered."""
+        import torch
+        n, d = int(opacities.shape[0]), int(sh_degree)
+        if not 0 <= d <= 3:
+            raise _abi.PtgsError(f"sh_degree {sh_degree}: 0..3")
+        k = (d + 1) ** 2
+        ls, lo, sh = out if out is not None else (
+            torch.empty_like(scales), torch.empty_like(opacities),
+            torch.empty((n, k, 3), dtype=torch.float32, device=scales.device))
+        self._f32(("scales", scales, n * 3), ("opacities", opacities, n), ("colors", colors, n * 3),
+                  ("log_scales", ls, n * 3), ("opacity_logits", lo, n), ("sh", sh, n * k * 3))
+        rc = self.lib.ptgs_gaussians_checkpoint_init(self._h, _ptr(scales), _ptr(opacities), _ptr(colors), n, d,
+                                                     _ptr(ls), _ptr(lo), _ptr(sh), _stream(stream))
+        self._chk(rc, "ptgs_gaussians_checkpoint_init")
+        return ls, lo, sh
+
+    def image_mse(self, image, target, out=None, stream=None):
+        """ptgs_image_mse: the summed squared error over the rgb of image [H, W, 4] against target [H, W, 3 or 4]
+        (contiguous float32 device tensors) as a float64 device tensor [1] (`out`, or a new one) that is not read
+        back here: mse = sum / (3 W H), PSNR = -10 log10(mse). A fixed summation order: two runs give the same
+        bits. Stream-ordered. An empty image leaves `out` as it is (a new one: 0)."""
+        import torch
+        if image.dim() != 3 or int(image.shape[2]) != 4:
+            raise _abi.PtgsError(f"image must be [H, W, 4] (got {tuple(image.shape)})")
+        h, w = int(image.shape[0]), int(image.shape[1])
+        c = int(target.shape[2]) if target.dim() == 3 else 0
+        if c not in (3, 4) or tuple(target.shape[:2]) != (h, w):
+            raise _abi.PtgsError(f"target must be [{h}, {w}, 3 or 4] (got {tuple(target.shape)})")
+        if out is None:
+            out = torch.zeros(1, dtype=torch.float64, device=image.device)
+        elif out.dtype != torch.float64 or out.numel() != 1:
+            raise _abi.PtgsError("out must be one float64")
+        self._f32(("image", image, h * w * 4), ("target", target, h * w * c))
+        rc = self.lib.ptgs_image_mse(self._h, _ptr(image) or None, _ptr(target) or None, c, w, h, _ptr(out),
+                                     _stream(stream))
+        self._chk(rc, "ptgs_image_mse")
+        return out
+
     def permute_sh(self, sh, ids, stream=None):
         """ptgs_gaussians_permute_sh: sh[ids] as a new tensor: the SH rows of the copy that
         sort_gaussians_spatial returned with these ids."""
