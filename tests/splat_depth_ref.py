@@ -32,12 +32,14 @@ def view_depth(means, view, dtype):
     return -(means @ V[2, :3] + V[2, 3])
 
 
-def evaluate(g, ubo, W, H, bg, frame, dL_dout, dL_dinv, dtype=torch.float64):
+def evaluate(g, ubo, W, H, bg, frame, dL_dout, dL_dinv, dtype=torch.float64, border=None):
     """g: dict of numpy arrays; frame: oracle.splat_gaussians(g, ubo, W, H, bg); dL_dout [H, W, 4], dL_dinv [H, W].
     Returns {"image" [H, W, 4], "invdepth" [H, W], "grads" / "grads_color" / "grads_depth" {GRAD_KEYS + "invd":
     numpy float64}, "borderline", "border_pixels" [H, W] bool (as splat_grad_ref.evaluate counts them), "clamped",
     "stopped", "empty" [H, W] bool: the pixels of tiles without a list}.
-    "invd" is dL/d(1 / d) per Gaussian, the tenth sum of the blend backward."""
+    "invd" is dL/d(1 / d) per Gaussian, the tenth sum of the blend backward.
+    border: the relative window around a threshold that counts as borderline (default splat_grad_ref.BORDER)."""
+    border = R.BORDER if border is None else border
     n = g["means"].shape[0]
     leaf = {k: torch.tensor(np.asarray(g[k], np.float64), dtype=dtype, requires_grad=True)
             for k in ("means", "scales", "rotations", "opacities", "colors")}
@@ -92,9 +94,9 @@ def evaluate(g, ubo, W, H, bg, frame, dL_dout, dL_dinv, dtype=torch.float64):
             pos = torch.arange(len(ids))[None, :]
             active = pos < first[:, None]
             seen = pos <= first[:, None]  # evaluated entries (the stopping one included)
-            near_skip = seen & ((ed * 255.0 - 1.0).abs() < R.BORDER)
-            near_clamp = seen & ((ed / 0.99 - 1.0).abs() < R.BORDER)
-            near_stop = (seen & ((keep / 1e-4 - 1.0).abs() < R.BORDER)).any(1)
+            near_skip = seen & ((ed * 255.0 - 1.0).abs() < border)
+            near_clamp = seen & ((ed / 0.99 - 1.0).abs() < border)
+            near_stop = (seen & ((keep / 1e-4 - 1.0).abs() < border)).any(1)
             borderline += int(near_skip.sum()) + int(near_clamp.sum()) + int(near_stop.sum())
             border_pixels[py.numpy(), px.numpy()] = (near_skip.any(1) | near_clamp.any(1) | near_stop).numpy()
             clamped_n += int((active & clamp & ~skip).sum())
