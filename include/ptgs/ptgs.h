@@ -408,6 +408,11 @@ typedef struct ptgs_scene_tree_opt {
     double ms;              /* host time the optimiser took at upload */
 } ptgs_scene_tree_opt;
 int ptgs_scene_get_tree_opt(const ptgs_ctx* ctx, ptgs_scene_tree_opt* out);
+/* The megakernel's traversal stack for the resident scene (each pointer may be NULL): the entries it keeps in
+ * LDS per lane, the worst-case stack entries of the copy it walks (optimised or not), and 1 when that need
+ * reaches the LDS depth, so that the instantiation with the private overflow is launched. ptgs_scene_build's
+ * deep_stack says the same of the canonical tree and the kernels that walk it (torus, depth, wavefront). */
+int ptgs_scene_get_pt_stack(const ptgs_ctx* ctx, uint32_t* lds_depth, uint32_t* walked_need, uint32_t* deep);
 
 /* ---------------- path tracer (raygen_camera.rgen + closesthit/miss/shadow) ---------------- */
 

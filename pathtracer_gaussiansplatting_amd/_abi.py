@@ -247,6 +247,7 @@ SYMBOLS = {
     "ptgs_scene_get_bvh": (_I, [_P, C.POINTER(BvhBuffers)]),
     "ptgs_scene_get_build": (_I, [_P, C.POINTER(SceneBuild)]),
     "ptgs_scene_get_tree_opt": (_I, [_P, C.POINTER(SceneTreeOpt)]),
+    "ptgs_scene_get_pt_stack": (_I, [_P, C.POINTER(_U), C.POINTER(_U), C.POINTER(_U)]),
     "ptgs_trace_camera": (_I, [_P, C.POINTER(Ubo), _U, _U, _P, _U, _U, _U, _P]),
     "ptgs_trace_camera_rows": (_I, [_P, C.POINTER(Ubo), _U, _U, _U, _U, _P, _U, _U, _U, _P]),
     "ptgs_trace_torus": (_I, [_P, C.POINTER(Ubo), C.POINTER(RayPush), _P, _U, _P, _P]),

@@ -61,6 +61,7 @@ struct ptgs_ctx {
   ptgs_scene_info info{};
   ptgs_scene_build build{};  // which builder's tree is resident (ptgs_scene_get_build)
   ptgs_scene_tree_opt tree_opt{};  // the megakernel's traversal copy of it (ptgs_scene_get_tree_opt)
+  uint32_t pt_walked_need = 0;     // that copy's stack need, optimised or not (ptgs_scene_get_pt_stack)
   unsigned long long* counters = nullptr;  // 8 x u64
   SplatFrames frames;  // the splat frame calls' workspaces, streams, events, run and pending reports
   DensifyWorkspace* densify = nullptr;  // the densification plan (ptgs_gaussians_densify_plan / _apply)
@@ -320,9 +321,11 @@ int check_node_window(ptgs_ctx* c) {
 // carries the child's entry distance in the bits left (bvh.h stack_layout, stack_key.h).
 // PTGS_PT_STACK_KEY_BITS forces the key's width (tests: 0 = never cull).
 // The copy's topology is its own: the trees of the two SAH builders (the same canonical tree) are rebuilt by
-// reinsertion for fewer node steps per ray (bvh_opt.h), held to the stack bound the canonical tree's kernel
-// instantiation assumes; the LBVH, whose point is rebuild time, is converted as it is. PTGS_PT_TREE_OPT=0 / 1
-// forces it off / on. The canonical nodes, scene_info and scene_build describe the canonical tree either way.
+// reinsertion for fewer node steps per ray (bvh_opt.h), held to the megakernel's own LDS stack (PTGS_PT_STACK) or,
+// failing that, to LDS + overflow; the LBVH, whose point is rebuild time, is converted as it is.
+// PTGS_PT_TREE_OPT=0 / 1 forces it off / on. The megakernel's instantiation follows the need of the copy it
+// walks (pt_deep_stack), not the canonical need (deep_stack: the torus, depth and wavefront kernels). The
+// canonical nodes, scene_info and scene_build describe the canonical tree either way.
 int upload_traversal_nodes(ptgs_ctx* c, std::vector<float>& host_n4, DevScene& s) {
   const size_t nf = (size_t)c->info.num_bvh_nodes * 32;
   if (host_n4.size() != nf) {
@@ -336,11 +339,17 @@ int upload_traversal_nodes(ptgs_ctx* c, std::vector<float>& host_n4, DevScene& s
   std::vector<uint32_t> n64;
   StackLayout sl;
   TreeOptInfo oi;
-  if (!make_opt_traversal_nodes(host_n4.data(), c->info.num_bvh_nodes, (int)c->build.fan,
-                                s.deep_stack ? PTGS_STACK_TOTAL : PTGS_STACK, optimise, force, n64, sl, oi))
+  // the copy's need is held below the megakernel's own LDS stack (the budgeted collapse, bvh_opt.h); only a
+  // tree whose reinserted BVH2 is too high for that is held to LDS + overflow and walked by the DEEP megakernel
+  const uint32_t limits[2] = {PTGS_PT_STACK, PTGS_STACK_TOTAL};
+  if (!make_opt_traversal_nodes(host_n4.data(), c->info.num_bvh_nodes, (int)c->build.fan, limits, 2, optimise, force,
+                                n64, sl, oi))
     return fail(c, PTGS_ERANGE, "BVH node extents beyond the compact nodes' step range (2^-100 .. 2^100)");
   c->tree_opt = ptgs_scene_tree_opt{oi.applied, oi.num_nodes, oi.need, oi.depth, oi.fan, oi.passes,
                                     oi.area_before, oi.area_after, oi.ms};
+  // the launch rule: the need of the copy that is walked (the canonical tree's when it was converted as it is)
+  c->pt_walked_need = oi.applied ? oi.need : c->build.stack_need;
+  s.pt_deep_stack = c->pt_walked_need >= PTGS_PT_STACK ? 1 : 0;
   s.stk_key_mask = sl.key_mask;
   s.leaf_shift = sl.leaf_shift;
   s.leaf_start_mask = sl.leaf_start_mask;
@@ -350,6 +359,8 @@ int upload_traversal_nodes(ptgs_ctx* c, std::vector<float>& host_n4, DevScene& s
               "fan %u, area sum %.3f -> %.3f\n", oi.applied ? "optimised" : "not applied", oi.ms, oi.passes,
               c->info.num_bvh_nodes, oi.num_nodes, c->build.stack_need, oi.need, c->info.bvh_depth, oi.depth, oi.fan,
               oi.area_before, oi.area_after);
+    fprintf(stderr, "[ptgs] megakernel: walked need %u, LDS stack %u%s\n", c->pt_walked_need, (uint32_t)PTGS_PT_STACK,
+            s.pt_deep_stack ? " (DEEP)" : "");
     fprintf(stderr, "[ptgs] stack word:%u link bits, %u key bits (mask %08x), leaf shift %u\n", sl.ref_bits, sl.key_bits,
             sl.key_mask, sl.leaf_shift);
   }
@@ -580,6 +591,15 @@ int ptgs_scene_get_tree_opt(const ptgs_ctx* c, ptgs_scene_tree_opt* out) {
   if (!c || !out) return PTGS_EINVAL;
   if (!c->has_scene) return PTGS_ENOSCENE;
   *out = c->tree_opt;
+  return PTGS_OK;
+}
+
+int ptgs_scene_get_pt_stack(const ptgs_ctx* c, uint32_t* lds_depth, uint32_t* walked_need, uint32_t* deep) {
+  if (!c) return PTGS_EINVAL;
+  if (!c->has_scene) return PTGS_ENOSCENE;
+  if (lds_depth) *lds_depth = c->dsc.pt_deep_stack ? PTGS_STACK : PTGS_PT_STACK;  // (pt_kernels.hip pt_lds_stack)
+  if (walked_need) *walked_need = c->pt_walked_need;
+  if (deep) *deep = c->dsc.pt_deep_stack ? 1u : 0u;
   return PTGS_OK;
 }
 

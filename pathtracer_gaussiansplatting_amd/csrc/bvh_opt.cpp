@@ -203,7 +203,130 @@ void emit_bvh2(const Tree2& t, std::vector<float>& n2) {
   }
 }
 
+// collapse_bvh4's entry and its float area (bvh.cpp), restated: the budgeted collapse orders by the same numbers
+struct Ent4 {
+  float lo[3], hi[3];
+  int32_t ref;
+};
+void bvh2_children(const float* n, Ent4 e[2]) {
+  int32_t c0, c1;
+  std::memcpy(&c0, &n[12], 4);
+  std::memcpy(&c1, &n[13], 4);
+  e[0] = Ent4{{n[0], n[2], n[8]}, {n[1], n[3], n[9]}, c0};
+  e[1] = Ent4{{n[4], n[6], n[10]}, {n[5], n[7], n[11]}, c1};
+}
+float ent_area(const Ent4& e) {
+  float d[3];
+  for (int a = 0; a < 3; ++a) d[a] = std::max(0.0f, e.hi[a] - e.lo[a]);
+  return d[0] * d[1] + d[1] * d[2] + d[2] * d[0];
+}
+
+// interior height of every BVH2 node (a node of two leaves: 1), children after parents (emit_bvh2, build_bvh)
+void bvh2_heights(const std::vector<float>& n2, std::vector<uint32_t>& h) {
+  const size_t num = n2.size() / 16;
+  h.assign(num, 0u);
+  for (size_t i = num; i-- > 0;) {
+    uint32_t m = 0;
+    for (int k = 0; k < 2; ++k) {
+      int32_t c;
+      std::memcpy(&c, &n2[16 * i + 12 + k], 4);
+      if (c >= 0) m = std::max(m, h[(size_t)c]);
+    }
+    h[i] = 1u + m;
+  }
+}
+
 }  // namespace
+
+uint32_t bvh2_height(const std::vector<float>& n2) {
+  std::vector<uint32_t> h;
+  bvh2_heights(n2, h);
+  return h.empty() ? 0u : h[0];
+}
+
+bool collapse_bvh4_budget(const std::vector<float>& n2, std::vector<float>& n4, uint32_t& num4, uint32_t& max_stack,
+                          uint32_t& depth4, int max_children, uint32_t need_limit) {
+  n4.clear();
+  num4 = 0; max_stack = 0; depth4 = 0;
+  std::vector<uint32_t> h2;
+  bvh2_heights(n2, h2);
+  if (h2.empty() || need_limit == 0 || h2[0] >= need_limit) return false;
+  max_children = std::max(2, std::min(4, max_children));
+  auto height = [&](const Ent4& e) { return e.ref >= 0 ? h2[(size_t)e.ref] : 0u; };
+  struct Item { int32_t b2; uint32_t slot, budget; };
+  std::vector<Item> queue;  // breadth first, as collapse_bvh4: the same slots when no budget binds
+  std::vector<std::vector<uint32_t>> kids;
+  std::vector<uint32_t> ncount;
+  queue.push_back(Item{0, 0u, need_limit - 1u});
+  n4.assign(32, 0.0f);
+  kids.emplace_back();
+  ncount.push_back(0);
+  for (size_t q = 0; q < queue.size(); ++q) {
+    const Item it = queue[q];  // (budget >= the node's height >= 1: its two children fit budget - 1)
+    Ent4 list[4];
+    int cnt = 2;
+    bvh2_children(&n2[16 * (size_t)it.b2], list);
+    while (cnt < max_children) {
+      // interior children by descending area (ties: the first, collapse_bvh4's choice); the first whose opening
+      // leaves every child a height within budget - cnt (cnt + 1 children: cnt entries pushed above them)
+      int order[4], no = 0;
+      for (int k = 0; k < cnt; ++k)
+        if (list[k].ref >= 0) order[no++] = k;
+      std::stable_sort(order, order + no, [&](int a, int b) { return ent_area(list[a]) > ent_area(list[b]); });
+      int best = -1;
+      Ent4 sub[2];
+      for (int o = 0; o < no && best < 0; ++o) {
+        if (it.budget < (uint32_t)cnt) break;
+        const uint32_t room = it.budget - (uint32_t)cnt;
+        bvh2_children(&n2[16 * (size_t)list[order[o]].ref], sub);
+        bool fits = height(sub[0]) <= room && height(sub[1]) <= room;
+        for (int k = 0; k < cnt && fits; ++k)
+          if (k != order[o]) fits = height(list[k]) <= room;
+        if (fits) best = order[o];
+      }
+      if (best < 0) break;
+      list[best] = sub[0];
+      list[cnt++] = sub[1];
+    }
+    float* f = &n4[32 * (size_t)it.slot];
+    for (int j = 0; j < 4; ++j) {
+      int32_t child = 0;
+      if (j < cnt) {
+        for (int a = 0; a < 3; ++a) {
+          f[(2 * a) * 4 + j] = list[j].lo[a];
+          f[(2 * a + 1) * 4 + j] = list[j].hi[a];
+        }
+        if (list[j].ref >= 0) {
+          const uint32_t ni = (uint32_t)(n4.size() / 32);
+          n4.resize(n4.size() + 32, 0.0f);
+          f = &n4[32 * (size_t)it.slot];  // (resize may move the storage)
+          queue.push_back(Item{list[j].ref, ni, it.budget - (uint32_t)(cnt - 1)});
+          kids.emplace_back();
+          ncount.push_back(0);
+          kids[it.slot].push_back(ni);
+          child = (int32_t)ni;
+        } else {
+          child = list[j].ref;
+        }
+      } else {
+        for (int a = 0; a < 6; ++a) f[a * 4 + j] = 1e30f;  // empty: a point box no ray reaches
+      }
+      std::memcpy(&f[24 + j], &child, 4);
+    }
+    ncount[it.slot] = (uint32_t)cnt;
+  }
+  num4 = (uint32_t)(n4.size() / 32);
+  std::vector<uint32_t> need(num4, 0), dep(num4, 1);
+  for (size_t i = num4; i-- > 0;) {
+    uint32_t m = 0, d = 0;
+    for (uint32_t k : kids[i]) { m = std::max(m, need[k]); d = std::max(d, dep[k]); }
+    need[i] = (ncount[i] - 1) + m;
+    dep[i] = 1 + d;
+  }
+  max_stack = need[0];
+  depth4 = dep[0];
+  return max_stack < need_limit;
+}
 
 double bvh4_area_sum(const float* n4, uint32_t num) {
   double sum = 0.0, root = 0.0;
@@ -231,6 +354,11 @@ double bvh4_area_sum(const float* n4, uint32_t num) {
 
 bool optimize_bvh4(const float* n4, uint32_t num, int fan, uint32_t need_limit, std::vector<float>& out,
                    TreeOptInfo& info, int passes) {
+  return optimize_bvh4(n4, num, fan, &need_limit, 1, out, info, passes);
+}
+
+bool optimize_bvh4(const float* n4, uint32_t num, int fan, const uint32_t* limits, int num_limits,
+                   std::vector<float>& out, TreeOptInfo& info, int passes) {
   const auto t0 = std::chrono::steady_clock::now();
   info = TreeOptInfo{};
   out.clear();
@@ -253,16 +381,25 @@ bool optimize_bvh4(const float* n4, uint32_t num, int fan, uint32_t need_limit, 
   info.passes = (uint32_t)std::max(0, passes);
   std::vector<float> n2;
   emit_bvh2(t, n2);
-  for (int f = std::max(2, std::min(4, fan)); f >= 2; --f) {
-    uint32_t num4 = 0, need = 0, depth4 = 0;
-    collapse_bvh4(n2, out, num4, need, depth4, f);
-    if (need >= need_limit) continue;
-    info.num_nodes = num4;
-    info.need = need;
-    info.depth = depth4;
-    info.fan = (uint32_t)f;
-    info.area_after = bvh4_area_sum(out.data(), num4);
-    return done(true);
+  info.height2 = bvh2_height(n2);
+  const int fan0 = std::max(2, std::min(4, fan));
+  for (int l = 0; l < num_limits; ++l) {
+    const uint32_t need_limit = limits[l];
+    for (int f = fan0; f >= 2; --f) {
+      uint32_t num4 = 0, need = 0, depth4 = 0;
+      collapse_bvh4(n2, out, num4, need, depth4, f);
+      // the greedy collapse's need does not fit: at the canonical fan-out, the collapse that narrows only the
+      // paths that set it (false when the BVH2's height reaches the limit: the lower fan-outs, as before)
+      if (need >= need_limit && !(f == fan0 && collapse_bvh4_budget(n2, out, num4, need, depth4, f, need_limit)))
+        continue;
+      info.num_nodes = num4;
+      info.need = need;
+      info.depth = depth4;
+      info.fan = (uint32_t)f;
+      info.limit = need_limit;
+      info.area_after = bvh4_area_sum(out.data(), num4);
+      return done(true);
+    }
   }
   return done(false);
 }
@@ -270,9 +407,15 @@ bool optimize_bvh4(const float* n4, uint32_t num, int fan, uint32_t need_limit, 
 bool make_opt_traversal_nodes(const float* n4, uint32_t num, int fan, uint32_t need_limit, bool optimise,
                               int force_key_bits, std::vector<uint32_t>& n64, StackLayout& layout, TreeOptInfo& info,
                               std::vector<float>* walked) {
+  return make_opt_traversal_nodes(n4, num, fan, &need_limit, 1, optimise, force_key_bits, n64, layout, info, walked);
+}
+
+bool make_opt_traversal_nodes(const float* n4, uint32_t num, int fan, const uint32_t* limits, int num_limits,
+                              bool optimise, int force_key_bits, std::vector<uint32_t>& n64, StackLayout& layout,
+                              TreeOptInfo& info, std::vector<float>* walked) {
   info = TreeOptInfo{};
   std::vector<float> opt;
-  if (optimise && optimize_bvh4(n4, num, fan, need_limit, opt, info)) {
+  if (optimise && optimize_bvh4(n4, num, fan, limits, num_limits, opt, info)) {
     if (make_traversal_nodes(opt.data(), info.num_nodes, force_key_bits, n64, layout)) {
       if (walked) walked->swap(opt);
       return true;

@@ -46,6 +46,8 @@ struct DevScene {
   int32_t uses_textures;          // some material has a texture index > 0: launch the TEX kernels
   int32_t deep_stack;             // the tree's worst-case stack need exceeds PTGS_STACK: launch the
                                   // kernels with the stack overflow (OVF = PTGS_STACK_OVF)
+  int32_t pt_deep_stack;          // the megakernel's: the need of the copy it walks (nodes64) reaches
+                                  // PTGS_PT_STACK: launch pt_camera_kernel's DEEP instantiation
   uint32_t num_light_cdf;
   uint32_t num_plights;
   int32_t bn_size;
@@ -133,6 +135,21 @@ __device__ __forceinline__ void pt_lanes_flush(const PtLaneCounts& c) {
 #define PTGS_STACK_OVF 9  // overflow entries beyond the LDS part
 #endif
 #define PTGS_STACK_TOTAL (PTGS_STACK + PTGS_STACK_OVF)
+// The megakernel (pt_camera_kernel) keeps an LDS stack of its own depth, PTGS_PT_STACK: it walks a copy of the
+// tree whose topology is its own (bvh_opt.h), collapsed under the budget need < PTGS_PT_STACK, so its stack may
+// be shorter than the canonical tree's need and more one-wave workgroups share a CU's LDS (pt_kernels.hip
+// PTGS_PT_MIN_WAVES). 30 entries are 7 680 B = 6 x 1 280 B: 20 workgroups in 160 KiB. The runtime's occupancy
+// query says 20 per CU for 32 entries (8 192 B) as well, but 31 and 32 entries time like fewer resident
+// workgroups (-3% against the 4-wave kernel where 30 gives +2.8%, pt_kernels.hip), as an allocation in blocks of
+// 1 280 B (160 KiB / 128) would make them: 30 is the depth. Its DEEP instantiations keep PTGS_STACK entries in LDS
+// and PTGS_STACK_OVF in the overflow, so every tree that fits PTGS_STACK_TOTAL still runs. The launch rule is
+// DevScene::pt_deep_stack: the walked copy's need >= PTGS_PT_STACK (a write past the LDS stack would land in
+// another lane's entries, silently). The torus, depth and wavefront kernels walk the canonical nodes and keep
+// PTGS_STACK.
+#ifndef PTGS_PT_STACK
+#define PTGS_PT_STACK 30
+#endif
+static_assert(PTGS_PT_STACK >= 2 && PTGS_PT_STACK <= PTGS_STACK, "the megakernel's LDS stack depth");
 #define PTGS_BLOCK 256
 
 PTGS_HD float i2f(int x) { union { int i; float f; } c; c.i = x; return c.f; }
@@ -540,7 +557,8 @@ __device__ __forceinline__ int enter_box4(Box4& b, Push push, Pop pop) {
 }
 
 // SS: the LDS stack's stride (work-items sharing it); OVF: overflow entries beyond the LDS part (0 for
-// a tree whose stack need fits PTGS_STACK: the overflow's branches and scratch cost 3.4% on C3)
+// a tree whose stack need fits the LDS part: the overflow's branches and scratch cost 3.4% on C3); LDS: the
+// LDS part's entries (PTGS_STACK; the megakernel's PTGS_PT_STACK)
 // N64: fetch the compact nodes (box4_q); their links are packed (stack_key.h): an interior index as it is,
 // a leaf with its count right above the first triangle's bits, so that the link takes the fewest bits the
 // tree needs (C3: 21, C5: 23) and the sign still tells a leaf.
@@ -589,7 +607,7 @@ __device__ __forceinline__ int enter_box4(Box4& b, Push push, Pop pop) {
 #ifndef PTGS_PT_ULOOP_ANY  // the same test in trace_any's single-exit walk
 #define PTGS_PT_ULOOP_ANY PTGS_PT_ULOOP
 #endif
-template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF, bool N64 = false, bool CULL = false>
+template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF, bool N64 = false, bool CULL = false, int LDS = PTGS_STACK>
 __device__ __forceinline__ Hit trace_closest(const DevScene& sc, const Ray& r, uint32_t seed, int* stack,
                                              TraversalCounters& cnt) {
   static_assert(!CULL || N64, "the distance key needs the compact nodes' packed links");
@@ -610,15 +628,15 @@ __device__ __forceinline__ Hit trace_closest(const DevScene& sc, const Ray& r, u
   int ovf[OVF > 0 ? OVF : 1];  // entries beyond the LDS part (private: scratch)
   auto push = [&](int c, float tn) {
     const int x = CULL ? (int)stack_pack((uint32_t)c, tn, kmask) : c;
-    if (OVF == 0 || sp < PTGS_STACK) stack[sp * SS] = x;
-    else ovf[sp - PTGS_STACK] = x;
+    if (OVF == 0 || sp < LDS) stack[sp * SS] = x;
+    else ovf[sp - LDS] = x;
     ++sp;
   };
   auto pop = [&]() -> int {
     if (!CULL) {
       if (!sp) return DONE;
       --sp;
-      return (OVF == 0 || sp < PTGS_STACK) ? stack[sp * SS] : ovf[sp - PTGS_STACK];
+      return (OVF == 0 || sp < LDS) ? stack[sp * SS] : ovf[sp - LDS];
     }
     const float cap = h.t * 1.0000004f;
     uint32_t x;
@@ -626,7 +644,7 @@ __device__ __forceinline__ Hit trace_closest(const DevScene& sc, const Ray& r, u
       x = (uint32_t)DONE;
       if (sp) {
         --sp;
-        x = (uint32_t)((OVF == 0 || sp < PTGS_STACK) ? stack[sp * SS] : ovf[sp - PTGS_STACK]);
+        x = (uint32_t)((OVF == 0 || sp < LDS) ? stack[sp * SS] : ovf[sp - LDS]);
       }
     } while (stack_bound(x, kmask) > cap);
     return (int)stack_link(x, kmask);
@@ -640,7 +658,7 @@ __device__ __forceinline__ Hit trace_closest(const DevScene& sc, const Ray& r, u
       uint32_t x = (uint32_t)DONE;
       if (sp) {
         --sp;
-        x = (uint32_t)((OVF == 0 || sp < PTGS_STACK) ? stack[sp * SS] : ovf[sp - PTGS_STACK]);
+        x = (uint32_t)((OVF == 0 || sp < LDS) ? stack[sp * SS] : ovf[sp - LDS]);
       }
       n = CULL ? (int)stack_link(x, kmask) : (int)x;
       again = CULL && stack_bound(x, kmask) > cap;
@@ -790,7 +808,7 @@ __device__ __forceinline__ bool leaf_any(const DevScene& sc, const Ray& r, int l
   return occ;
 }
 
-template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF, bool N64 = false>  // (as trace_closest)
+template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF, bool N64 = false, int LDS = PTGS_STACK>  // (as trace_closest)
 __device__ __forceinline__ bool trace_any(const DevScene& sc, const Ray& r, uint32_t seed, int* stack,
                                           TraversalCounters& cnt) {
   const Ray rq = node64_ray<N64>(r);
@@ -801,14 +819,14 @@ __device__ __forceinline__ bool trace_any(const DevScene& sc, const Ray& r, uint
   const int DONE = 0x7fffffff;
   bool occluded = false;
   auto push = [&](int c) {
-    if (OVF == 0 || sp < PTGS_STACK) stack[sp * SS] = c;
-    else ovf[sp - PTGS_STACK] = c;
+    if (OVF == 0 || sp < LDS) stack[sp * SS] = c;
+    else ovf[sp - LDS] = c;
     ++sp;
   };
   auto pop = [&]() -> int {
     if (!sp) return DONE;
     --sp;
-    return (OVF == 0 || sp < PTGS_STACK) ? stack[sp * SS] : ovf[sp - PTGS_STACK];
+    return (OVF == 0 || sp < LDS) ? stack[sp * SS] : ovf[sp - LDS];
   };
   int leaf = DONE;  // (PARK: the postponed leaf)
   for (;;) {
@@ -869,7 +887,7 @@ __device__ __forceinline__ bool trace_any(const DevScene& sc, const Ray& r, uint
 #else
   auto pop_nz = [&]() -> int {  // sp > 0
     --sp;
-    return (OVF == 0 || sp < PTGS_STACK) ? stack[sp * SS] : ovf[sp - PTGS_STACK];
+    return (OVF == 0 || sp < LDS) ? stack[sp * SS] : ovf[sp - LDS];
   };
   while (true) {
     while (node >= 0) {
@@ -888,8 +906,8 @@ __device__ __forceinline__ bool trace_any(const DevScene& sc, const Ray& r, uint
             next = b.c[j];
             have = true;
           } else {
-            if (OVF == 0 || sp < PTGS_STACK) stack[sp * SS] = b.c[j];
-            else ovf[sp - PTGS_STACK] = b.c[j];
+            if (OVF == 0 || sp < LDS) stack[sp * SS] = b.c[j];
+            else ovf[sp - LDS] = b.c[j];
             ++sp;
           }
         }
@@ -1100,13 +1118,13 @@ __device__ __forceinline__ void shadow_towards(ShadowQuery& q, v3 o, v3 light_po
   q.tmax = dist - 0.005f;
 }
 
-template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF, bool N64 = false>  // (as trace_closest)
+template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF, bool N64 = false, int LDS = PTGS_STACK>  // (as trace_closest)
 __device__ __forceinline__ void resolve_shadow(ShadeCtx& c, v3& color, uint32_t seed, const ShadowQuery& q,
                                                TraversalCounters& cnt) {
   if (!(q.flags & SQ_TRACE)) return;
   c.shadow_rays++;
   const Ray r = make_ray(q.o, q.d, 0.001f, q.tmax);
-  float vis = trace_any<STATS, TEX, SS, OVF, N64>(*c.sc, r, seed, c.stack, cnt) ? 0.0f : 1.0f;
+  float vis = trace_any<STATS, TEX, SS, OVF, N64, LDS>(*c.sc, r, seed, c.stack, cnt) ? 0.0f : 1.0f;
   vis = fmaxx(vis, q.trans);
   if (vis > 0.0f && (q.flags & SQ_VALID)) {
     v3 contrib = (q.pre * vis) * q.post;

@@ -56,14 +56,30 @@ __device__ __forceinline__ void flush_counters(unsigned long long* counters, uin
   }
 }
 
-// 4 waves per SIMD (<= 128 VGPRs; the 39-entry LDS stack allows no more workgroups anyway). With the
-// NEE shadow ray traced after shading (resolve_shadow) the timed instantiation keeps 96 B per lane of
-// scratch (spills in the shading code, once per bounce); round 1 held the shading state across the
-// shadow traversal and spilled 164 B per lane. PTGS_PT_MIN_WAVES=3 compiles without scratch and
-// measured 9% slower.
+// Waves per SIMD. The kernel waits on dependent node fetches (profiles/r11_summary.md: waves wait 40% of their
+// cycles at 4 per SIMD), so the plain instantiations are built for 5: <= 96 VGPRs, and an LDS stack short enough
+// for 20 one-wave workgroups per CU, PTGS_PT_STACK (pt_device.h), which the walked copy's budgeted collapse meets
+// (bvh_opt.h). At 5 the timed instantiation keeps 168 B per lane of scratch instead of 32 (TEX 216); every
+// scratch access is in the prologue, the per-sample set-up, the shading or the end of the bounce, none in a node
+// or triangle loop of either walk (tools/isa_loops.py). Measured on C3 at 64 spp, one process, interleaved
+// (tools/ab_pt.py; profiles/r12_summary.md): 4 waves + 39 entries 6 924 Mrays/s; 5 waves + 30 entries 7 115
+// (+2.8%); 5 waves + 31 or 32 entries 6 708 and 6 721 (-3%): 20 x 8 192 B is the whole 160 KiB and
+// hipOccupancyMaxActiveBlocksPerMultiprocessor answers 20 for it (tools/pt_occupancy.py), but only 7 680 B =
+// 6 x 1 280 B behaves as 20 resident workgroups: above it a CU holds fewer, and the spills are paid for nothing.
+// PTGS_PT_MIN_WAVES=3 compiles without scratch and measured 9% slower than 4; 6 waves (80 VGPRs)
+// would need a stack of about 25, below the height of C3's reinserted BVH2 (27): no collapse fits it.
+// The DEEP instantiations stay at 4 waves with PTGS_STACK LDS entries and PTGS_STACK_OVF overflow entries: a tree
+// whose reinserted BVH2 is too high for the budget (C5's 1M-triangle mesh: 31) walks the copy held to
+// PTGS_STACK_TOTAL, and at 5 waves with 30 + 18 entries (320 B per lane of scratch) it measured -6.9%
+// (4 996 -> 4 650 Mrays/s).
 #ifndef PTGS_PT_MIN_WAVES
-#define PTGS_PT_MIN_WAVES 4
+#define PTGS_PT_MIN_WAVES 5
 #endif
+#ifndef PTGS_PT_DEEP_MIN_WAVES
+#define PTGS_PT_DEEP_MIN_WAVES 4
+#endif
+// LDS stack entries per lane of pt_camera_kernel's plain and DEEP instantiations
+__host__ __device__ constexpr int pt_lds_stack(bool deep) { return deep ? PTGS_STACK : PTGS_PT_STACK; }
 
 // PT_STAMP builds (tools/pt_stamps.py): per-workgroup s_memrealtime (100 MHz) at start and end of
 // pt_camera_kernel, read back with ptgs_debug_pt_stamps (the schedule's tail)
@@ -79,9 +95,9 @@ __host__ __device__ __forceinline__ uint32_t pt_lanes_log2(uint32_t spp) {
   return (PTGS_PT_LPP >= 4 && spp >= 4u) ? 2u : (PTGS_PT_LPP >= 2 && spp >= 2u) ? 1u : 0u;
 }
 
-// DEEP: the traversal with the stack overflow (DevScene::deep_stack)
+// DEEP: the traversal with the stack overflow (DevScene::pt_deep_stack)
 template <bool STATS, bool TEX, bool DEEP>
-__global__ __launch_bounds__(PTGS_PT_WG, PTGS_PT_MIN_WAVES) void pt_camera_kernel(DevScene sc, CamParams cp, float4* __restrict__ accum,
+__global__ __launch_bounds__(PTGS_PT_WG, DEEP ? PTGS_PT_DEEP_MIN_WAVES : PTGS_PT_MIN_WAVES) void pt_camera_kernel(DevScene sc, CamParams cp, float4* __restrict__ accum,
                                                         uint32_t W, uint32_t H, uint32_t row0, uint32_t row1,
                                                         uint32_t spp, uint32_t frame0, uint32_t stride,
                                                         uint32_t mode, unsigned long long* counters,
@@ -131,7 +147,9 @@ __global__ __launch_bounds__(PTGS_PT_WG, PTGS_PT_MIN_WAVES) void pt_camera_kerne
 #endif
   const bool active = (x < W) && (y < row1);
 
-  __shared__ int s_stack[PTGS_STACK * PTGS_PT_WG];
+  constexpr int kLds = pt_lds_stack(DEEP);
+  constexpr int kOvf = DEEP ? PTGS_STACK_TOTAL - kLds : 0;  // (LDS + overflow: PTGS_STACK_TOTAL, as the other kernels)
+  __shared__ int s_stack[kLds * PTGS_PT_WG];
   ShadeCtx c; c.sc = &sc; c.cp = &cp; c.stack = s_stack + threadIdx.x; c.shadow_rays = 0;
   TraversalCounters tc; tc.nodes = 0; tc.tris = 0; tc.hits = 0;
   PT_LANES_INIT(tc);
@@ -182,14 +200,14 @@ __global__ __launch_bounds__(PTGS_PT_WG, PTGS_PT_MIN_WAVES) void pt_camera_kerne
         p.depth = depth;
         Ray ray = make_ray(ro, rd, 0.001f, 10000.0f);
         ext_rays++;
-        Hit h = trace_closest<STATS, TEX, PTGS_PT_WG, DEEP ? PTGS_STACK_OVF : 0, PTGS_PT_NODE64 != 0,
-                              PTGS_PT_NODE64 != 0 && PTGS_PT_STACK_CULL != 0>(sc, ray, p.seed, c.stack, tc);
+        Hit h = trace_closest<STATS, TEX, PTGS_PT_WG, kOvf, PTGS_PT_NODE64 != 0,
+                              PTGS_PT_NODE64 != 0 && PTGS_PT_STACK_CULL != 0, kLds>(sc, ray, p.seed, c.stack, tc);
         if (STATS && h.gid != 0xffffffffu) tc.hits++;
         ShadowQuery q;
         q.flags = 0;
         if (h.gid == 0xffffffffu) miss<false>(cp, p);
         else closest_hit<false, TEX>(c, p, ray, h, q);
-        resolve_shadow<STATS, TEX, PTGS_PT_WG, DEEP ? PTGS_STACK_OVF : 0, PTGS_PT_NODE64 != 0>(c, p.color, p.seed, q, tc);  // NEE visibility after shading
+        resolve_shadow<STATS, TEX, PTGS_PT_WG, kOvf, PTGS_PT_NODE64 != 0, kLds>(c, p.color, p.seed, q, tc);  // NEE visibility after shading
         acc = acc + p.color * thr;
         acc = vmin(acc, 5.0f);
         if (p.hit_flag < 0.0f) break;
@@ -428,6 +446,16 @@ void free_pt_sched(PtSched& ps) {
 // ------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------
+typedef void (*PtCameraKernel)(DevScene, CamParams, float4*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t,
+                               uint32_t, uint32_t, unsigned long long*, const uint32_t*, uint32_t*);
+static PtCameraKernel pt_camera_instantiation(bool stats, bool tex, bool deep) {
+  static const PtCameraKernel ks[8] = {
+      pt_camera_kernel<false, false, false>, pt_camera_kernel<false, false, true>, pt_camera_kernel<false, true, false>,
+      pt_camera_kernel<false, true, true>,   pt_camera_kernel<true, false, false>, pt_camera_kernel<true, false, true>,
+      pt_camera_kernel<true, true, false>,   pt_camera_kernel<true, true, true>};
+  return ks[(stats ? 4 : 0) + (tex ? 2 : 0) + (deep ? 1 : 0)];
+}
+
 hipError_t launch_pt_camera(const DevScene& sc, const CamParams& cp, float* accum, uint32_t W, uint32_t H,
                             uint32_t row0, uint32_t row1, uint32_t spp, uint32_t frame0, uint32_t stride,
                             uint32_t mode, unsigned long long* counters, bool stats, PtSched* ps,
@@ -476,13 +504,8 @@ hipError_t launch_pt_camera(const DevScene& sc, const CamParams& cp, float* accu
   }
 #endif
   // (STATS, TEX, DEEP) instantiations: TEX only for scenes whose materials reference textures, DEEP only
-  // for trees deeper than the LDS stack
-  static void (*const ks[8])(DevScene, CamParams, float4*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t,
-                             uint32_t, uint32_t, unsigned long long*, const uint32_t*, uint32_t*) = {
-      pt_camera_kernel<false, false, false>, pt_camera_kernel<false, false, true>, pt_camera_kernel<false, true, false>,
-      pt_camera_kernel<false, true, true>,   pt_camera_kernel<true, false, false>, pt_camera_kernel<true, false, true>,
-      pt_camera_kernel<true, true, false>,   pt_camera_kernel<true, true, true>};
-  auto k = ks[(stats ? 4 : 0) + (sc.uses_textures ? 2 : 0) + (sc.deep_stack ? 1 : 0)];
+  // when the walked copy's need reaches the megakernel's LDS stack (pt_deep_stack, not the canonical deep_stack)
+  auto k = pt_camera_instantiation(stats, sc.uses_textures != 0, sc.pt_deep_stack != 0);
   hipLaunchKernelGGL(k, grid, block, 0, stream, sc, cp, (float4*)accum, W, H, row0, row1, spp, frame0, stride, mode,
                      counters, order, cost);
   return hipGetLastError();
@@ -516,6 +539,27 @@ hipError_t launch_pt_torus(const DevScene& sc, const CamParams& cp, const TorusP
 }
 
 }  // namespace ptgs
+
+// (tools/pt_occupancy.py: what the runtime says of a pt_camera_kernel instantiation, bits stats 4 | tex 2 |
+// deep 1. Launches nothing. out: workgroups per CU the runtime would keep resident, static LDS bytes, VGPRs,
+// private bytes per lane, its LDS stack entries, its launch bound in waves per SIMD, PTGS_PT_WG.)
+extern "C" int ptgs_debug_pt_occupancy(unsigned int instantiation, unsigned int out[7]) {
+  const void* k = (const void*)ptgs::pt_camera_instantiation((instantiation & 4u) != 0, (instantiation & 2u) != 0,
+                                                             (instantiation & 1u) != 0);
+  int blocks = 0;
+  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k, PTGS_PT_WG, 0);
+  if (e) return (int)e;
+  hipFuncAttributes fa;
+  if ((e = hipFuncGetAttributes(&fa, k))) return (int)e;
+  out[0] = (unsigned int)blocks;
+  out[1] = (unsigned int)fa.sharedSizeBytes;
+  out[2] = (unsigned int)fa.numRegs;
+  out[3] = (unsigned int)fa.localSizeBytes;
+  out[4] = (unsigned int)ptgs::pt_lds_stack((instantiation & 1u) != 0);
+  out[5] = (instantiation & 1u) ? PTGS_PT_DEEP_MIN_WAVES : PTGS_PT_MIN_WAVES;
+  out[6] = PTGS_PT_WG;
+  return 0;
+}
 
 #ifdef PT_LANES
 // (diagnostic builds: the lane counts of pt_device.h PtLoop, read and cleared)

@@ -121,6 +121,15 @@ class Renderer:
         self._chk(self.lib.ptgs_scene_get_tree_opt(self._h, C.byref(t)), "ptgs_scene_get_tree_opt")
         return t
 
+    def scene_pt_stack(self) -> tuple:
+        """(LDS depth, walked need, deep) of the megakernel for the resident scene: the stack entries it keeps in
+        LDS per lane, the worst-case need of the copy it walks, and whether the instantiation with the private
+        overflow is launched (walked need >= LDS depth)."""
+        lds, need, deep = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._chk(self.lib.ptgs_scene_get_pt_stack(self._h, C.byref(lds), C.byref(need), C.byref(deep)),
+                  "ptgs_scene_get_pt_stack")
+        return lds.value, need.value, bool(deep.value)
+
     # ---------------------------------------------------------------- path tracer
     def trace_camera(self, ubo: Ubo, width: int, height: int, accum, spp: int = 1, frame_stride: int = 1,
                      mode: int = _abi.ACCUM_RUNNING_MEAN, rows: tuple | None = None, stream=None):
