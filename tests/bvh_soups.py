@@ -107,8 +107,25 @@ def offset(seed=6):
     return (soup(1500, seed).astype(np.float64) + np.asarray(OFFSET)).astype(np.float32)
 
 
-def scene(tri):
-    """A Scene of the triangles (one object, one mesh, one diffuse material, no lights), in this order."""
+def strip(x):
+    """Thin triangles side by side along x, one per interval of the ascending positions x (each 1 long in y,
+    slightly tilted in z), float32 [n, 9]."""
+    t = np.zeros((len(x) - 1, 9), np.float32)
+    t[:, 0], t[:, 3], t[:, 6] = x[:-1], x[1:], x[:-1]
+    t[:, 4] = 1.0
+    t[:, 7], t[:, 8] = 1.0, x[:-1] * np.float32(0.25)
+    return t
+
+
+def geometric_slivers(n, ratio, first=1e-5):
+    """A strip of n triangles, every one `ratio` times as wide as the one before (the first `first`): the SAH build
+    splits the wide end off again and again, so the tree is a chain and its stack need grows with n, not log n."""
+    return strip((np.float64(ratio) ** np.arange(n + 1) * first).astype(np.float32))
+
+
+def scene(tri, lights=()):
+    """A Scene of the triangles (one object, one mesh, one diffuse material), in this order. lights: scene-level
+    punctual lights (PUNCTUAL_LIGHT_DTYPE records, SceneBuilder.add_punctual_light); none by default."""
     tri = np.ascontiguousarray(tri, np.float32)
     n = len(tri)
     nrm = np.cross((tri[:, 1] - tri[:, 0]).astype(np.float64), (tri[:, 2] - tri[:, 0]).astype(np.float64))
@@ -124,7 +141,10 @@ def scene(tri):
     m = S.default_material()
     m["metallic_factor"] = 0.0
     m["base_color_factor"] = [0.8, 0.7, 0.6, 1.0]
-    sc = S.SceneBuilder().add_object(v, np.arange(3 * n, dtype=np.uint32), prims, m).finalize()
+    b = S.SceneBuilder().add_object(v, np.arange(3 * n, dtype=np.uint32), prims, m)
+    for light in lights:
+        b.add_punctual_light(light)
+    sc = b.finalize()
     sc.blue_noise = U.blue_noise()
     return sc
 

@@ -12,10 +12,10 @@ mark stays within the tree's stack need, and no lane outside the node loop write
 the modelled wave iterations of the three walks (run pytest -s to see them).
 
 GPU part: the megakernel against the CPU oracle (which walks its own tree): images bit for bit
-(np.array_equal), extension and shadow ray counts equal. The DEEP instantiation (stack need >= 39, entries in
-the private overflow) needs a tree of C5's size; no test scene builds one in under a second, so it remains
-covered by the existing C5 config test only. The wavefront tracer's shadow kernel keeps a walk of its own
-(pt_wavefront.hip); its case here guards the headers both tracers share."""
+(np.array_equal), extension and shadow ray counts equal. The DEEP instantiations (stack need >= 39, entries in
+the private overflow) and the wavefront tracer's shadow kernel, which keeps a walk of its own (pt_wavefront.hip),
+are tested on strips of a few dozen triangles in tests/test_pt_canonical_walks.py; the wavefront case here guards
+the headers both tracers share."""
 import os
 import shutil
 import subprocess

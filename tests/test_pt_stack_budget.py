@@ -24,6 +24,7 @@ import pytest
 
 import bvh_soups as B
 import scenes_util as U
+from bvh_soups import geometric_slivers as _geometric_slivers, strip as _strip
 from pathtracer_gaussiansplatting_amd import make_ubo
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -93,20 +94,6 @@ def _slivers(n=257):
     """A strip of thin triangles sorted along x (each 1e-3 wide, 1 long, slightly tilted)."""
     x = np.arange(n + 1, dtype=np.float32) * np.float32(1e-3)
     return _strip(x)
-
-
-def _geometric_slivers(n, ratio):
-    """The same strip with every triangle `ratio` times as wide as the one before (the first 1e-5): the SAH build
-    splits the wide end off again and again, so the tree is a chain and its stack need grows with n, not log n."""
-    return _strip((np.float64(ratio) ** np.arange(n + 1) * 1e-5).astype(np.float32))
-
-
-def _strip(x):
-    t = np.zeros((len(x) - 1, 9), np.float32)
-    t[:, 0], t[:, 3], t[:, 6] = x[:-1], x[1:], x[:-1]
-    t[:, 4] = 1.0
-    t[:, 7], t[:, 8] = 1.0, x[:-1] * np.float32(0.25)
-    return t
 
 
 # what tree_budget_check reports for the reinserted BVH2 of each mesh (opt_height2; test_budget_check pins them)
