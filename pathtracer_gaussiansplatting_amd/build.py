@@ -37,8 +37,8 @@ HOST_SOURCES = {"bvh_opt.cpp", "gltf.cpp", "image_decode.cpp", "ply.cpp", "sampl
 # pt_kernels.hip, -fno-slp-vectorize on top: what the SLP vectoriser still packs in the megakernel is f32 pairs
 # (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32: 260 in the timed instantiation, in the shading code and the shadow
 # leaf's triangle test), and packed f32 does not pay in this kernel: the explicit packing of the slab FMAs
-# (PTGS_PT_PK_SLAB, pt_device.h) measured -4.9% for 14 fewer instructions per node step, and the kernel without any
-# SLP packing +1.9% (C3 at 64 spp, tools/ab_pt.py, images identical; profiles/r10_summary.md).
+# (tools/patches/pt_pk_slab_rejected.patch) measured -4.9% for 14 fewer instructions per node step, and the kernel
+# without any SLP packing +1.9% (C3 at 64 spp, tools/ab_pt.py, images identical; profiles/r10_summary.md).
 EXTRA = {"pt_kernels.hip": ["-mllvm", "-simplifycfg-sink-common=false", "-mllvm", "-slp-vectorize-hor=false",
                             "-fno-slp-vectorize"],
          "pt_wavefront.hip": ["-mllvm", "-simplifycfg-sink-common=false", "-mllvm", "-slp-vectorize-hor=false"]}

@@ -28,7 +28,7 @@ namespace ptgs {
 struct DevScene {
   const float4* nodes;            // 8 float4 per 4-wide node (see bvh.h)
   const uint4* nodes64;           // the same nodes quantised to 4 uint4 (bvh.h quantize_bvh4): the
-                                  // megakernel's traversal reads these (PTGS_PT_NODE64)
+                                  // megakernel's traversal reads these (box4_q)
   const float4* tris;             // 3 float4 per triangle: (v0, mesh_bits) (e1, prim_bits) (e2, gid_bits)
   const uint32_t* tri_flags;      // bit0: non-opaque (any-hit shader runs)
   const ptgs_vertex* vertices;
@@ -177,27 +177,14 @@ __device__ __forceinline__ v3 ld3(const float* p) { return mk3(p[0], p[1], p[2])
 // ---------------------------------------------------------------------------------------------
 // Ray / box / triangle
 // ---------------------------------------------------------------------------------------------
-// PTGS_PT_NEARFAR: the box test reads each axis's near and far planes by the ray's direction signs
-// (byte offsets in the node, below) instead of ordering both slab distances with a min and a max:
-// the same slab values, 24 fewer VALU per 4-wide node
-#ifndef PTGS_PT_NEARFAR
-#define PTGS_PT_NEARFAR 1
-#endif
-// PTGS_PT_ASM_MIN: the far slab distance's min in inline asm: the compiler canonicalises the hit
-// distance (tcap, a loop-carried value it cannot prove canonical) before every fminf, one VALU per node:
-// C3 at 16 spp 5 380 -> 5 414 Mrays/s (tools/ab_pt.py, profiles/r05/pt_tweaks_ab.log). (Counting the hit
-// children from the sorted distances instead of a running count measured equal: 5 374.)
-#ifndef PTGS_PT_ASM_MIN
-#define PTGS_PT_ASM_MIN 1
-#endif
-
+// The box tests read each axis's near and far planes by the ray's direction signs (byte offsets in the node,
+// below) instead of ordering both slab distances with a min and a max: the same slab values, 24 fewer VALU
+// per 4-wide node.
 struct Ray {
   v3 o, d, inv;
   v3 oinv;  // o * inv: slab distances as one FMA per plane (box tests need conservativeness only)
   float tmin, tmax;
-#if PTGS_PT_NEARFAR
   uint32_t nx, ny, nz;  // byte offset in a node of the near plane per axis: lo (0 / 32 / 64) or hi (+16)
-#endif
 };
 
 __device__ __forceinline__ float safe_inv(float d) {
@@ -210,13 +197,11 @@ __device__ __forceinline__ Ray make_ray(v3 o, v3 d, float tmin, float tmax) {
   Ray r; r.o = o; r.d = d; r.tmin = tmin; r.tmax = tmax;
   r.inv = mk3(safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
   r.oinv = mk3(o.x * r.inv.x, o.y * r.inv.y, o.z * r.inv.z);
-#if PTGS_PT_NEARFAR
   // inv > 0: fma(lo, inv, -oinv) <= fma(hi, inv, -oinv) (the rounded FMA is monotone in lo / hi), so
   // the near plane is lo; inv < 0: hi (inv is never 0: safe_inv)
   r.nx = r.inv.x < 0.0f ? 16u : 0u;
   r.ny = r.inv.y < 0.0f ? 48u : 32u;
   r.nz = r.inv.z < 0.0f ? 80u : 64u;
-#endif
   return r;
 }
 
@@ -336,7 +321,14 @@ struct Box4 {
   unsigned long long hm[4];  // per child, the wave's lanes whose ray hits it (SGPR masks: the hit-count logic of
                              // enter_box4 runs on the scalar unit instead of a per-lane count in VGPRs)
 };
-#if PTGS_PT_NEARFAR
+// min(x1, y1, z1, tcap) in inline asm: the compiler canonicalises tcap (the hit distance, a loop-carried value it
+// cannot prove canonical) before every fminf, one VALU per node
+__device__ __forceinline__ float far_min(float x1, float y1, float z1, float tcap) {
+  float tf;
+  asm("v_min3_f32 %0, %1, %2, %3" : "=v"(tf) : "v"(x1), "v"(y1), "v"(z1));
+  asm("v_min_f32 %0, %1, %2" : "=v"(tf) : "v"(tf), "v"(tcap));
+  return tf;
+}
 __device__ __forceinline__ float4 node_ld(__amdgpu_buffer_rsrc_t rs, uint32_t off) {
   typedef unsigned int u4 __attribute__((ext_vector_type(4)));
   const u4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0);
@@ -352,7 +344,9 @@ __device__ __forceinline__ void box4(const Ray& r, const DevScene& sc, int node,
   const float4 ny = node_ld(rs, oy), fy = node_ld(rs, oy ^ 16u);
   const float4 nz = node_ld(rs, oz), fz = node_ld(rs, oz ^ 16u);
   float4 ch = node_ld(rs, base + 96u);
-  asm volatile("" : "+v"(ch.x), "+v"(ch.y), "+v"(ch.z), "+v"(ch.w));  // (pinned: box4 below)
+  // the child links share the node's cache line: pin them here so the compiler cannot sink their
+  // load into the hit branch (a second dependent L2 round trip per node): +4% Mrays/s
+  asm volatile("" : "+v"(ch.x), "+v"(ch.y), "+v"(ch.z), "+v"(ch.w));
   const float NX[4] = {nx.x, nx.y, nx.z, nx.w}, FX[4] = {fx.x, fx.y, fx.z, fx.w};
   const float NY[4] = {ny.x, ny.y, ny.z, ny.w}, FY[4] = {fy.x, fy.y, fy.z, fy.w};
   const float NZ[4] = {nz.x, nz.y, nz.z, nz.w}, FZ[4] = {fz.x, fz.y, fz.z, fz.w};
@@ -363,82 +357,30 @@ __device__ __forceinline__ void box4(const Ray& r, const DevScene& sc, int node,
     const float y0 = __builtin_fmaf(NY[j], r.inv.y, -r.oinv.y), y1 = __builtin_fmaf(FY[j], r.inv.y, -r.oinv.y);
     const float z0 = __builtin_fmaf(NZ[j], r.inv.z, -r.oinv.z), z1 = __builtin_fmaf(FZ[j], r.inv.z, -r.oinv.z);
     const float tn = fmaxf(fmaxf(x0, y0), fmaxf(z0, r.tmin));
-#if PTGS_PT_ASM_MIN
-    float tf;
-    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(tf) : "v"(x1), "v"(y1), "v"(z1));
-    asm("v_min_f32 %0, %1, %2" : "=v"(tf) : "v"(tf), "v"(tcap));
-#else
-    const float tf = fminf(fminf(x1, y1), fminf(z1, tcap));
-#endif
+    const float tf = far_min(x1, y1, z1, tcap);
     const bool h = tn <= tf * 1.0000004f;
     o.tn[j] = h ? tn : __builtin_huge_valf();
     o.c[j] = f2i(CH[j]);
     o.hm[j] = __builtin_amdgcn_ballot_w64(h);
   }
 }
-#else
-__device__ __forceinline__ void box4(const Ray& r, const DevScene& sc, int node, float tcap, Box4& o) {
-  const float4* np = sc.nodes + 8 * node;
-  const float4 lx = np[0], hx = np[1], ly = np[2], hy = np[3], lz = np[4], hz = np[5];
-  float4 ch = np[6];
-  // the child links share the node's cache line: pin them here so the compiler cannot sink their
-  // load into the hit branch (a second dependent L2 round trip per node): +4% Mrays/s
-  asm volatile("" : "+v"(ch.x), "+v"(ch.y), "+v"(ch.z), "+v"(ch.w));
-  const float LX[4] = {lx.x, lx.y, lx.z, lx.w}, HX[4] = {hx.x, hx.y, hx.z, hx.w};
-  const float LY[4] = {ly.x, ly.y, ly.z, ly.w}, HY[4] = {hy.x, hy.y, hy.z, hy.w};
-  const float LZ[4] = {lz.x, lz.y, lz.z, lz.w}, HZ[4] = {hz.x, hz.y, hz.z, hz.w};
-  const float CH[4] = {ch.x, ch.y, ch.z, ch.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float x0 = __builtin_fmaf(LX[j], r.inv.x, -r.oinv.x), x1 = __builtin_fmaf(HX[j], r.inv.x, -r.oinv.x);
-    const float y0 = __builtin_fmaf(LY[j], r.inv.y, -r.oinv.y), y1 = __builtin_fmaf(HY[j], r.inv.y, -r.oinv.y);
-    const float z0 = __builtin_fmaf(LZ[j], r.inv.z, -r.oinv.z), z1 = __builtin_fmaf(HZ[j], r.inv.z, -r.oinv.z);
-    const float tn = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), r.tmin));
-    const float tf = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fminf(fmaxf(z0, z1), tcap));
-    const bool h = tn <= tf * 1.0000004f;
-    o.tn[j] = h ? tn : __builtin_huge_valf();
-    o.c[j] = f2i(CH[j]);
-    o.hm[j] = __builtin_amdgcn_ballot_w64(h);
-  }
-}
-#endif
-// PTGS_PT_NODE64: the megakernel's traversals fetch the compact 64-B node (bvh.h quantize_bvh4): four
-// 16-B loads per lane instead of seven. Per node and axis the step and origin are folded into the ray's
+// The megakernel's traversals fetch the compact 64-B node (bvh.h quantize_bvh4; N64 below): four 16-B loads
+// per lane instead of seven. Per node and axis the step and origin are folded into the ray's
 // slab constants (one multiply, exact: the step is a power of two; one FMA), per child plane one byte
 // conversion and one FMA: t = fma(q, step * inv, fma(origin, inv, -oinv)). The direction sign picks the
-// near and far byte planes, as PTGS_PT_NEARFAR picks the float planes. The decoded box contains the
+// near and far byte planes, as it picks box4's float planes. The decoded box contains the
 // canonical padded box for every ray, so the visited nodes are a superset and the hits,
 // ray counts and image do not change. Slots 2 and 3 may be empty (link 0: the root, never a child):
 // they hold inverted planes, and the link is tested too so that no rounding can enter them.
-#ifndef PTGS_PT_NODE64
-#define PTGS_PT_NODE64 1
-#endif
-// PTGS_PT_NODE64_PIN: keep o * inv in registers across the walk (the compiler otherwise recomputes the
-// three products at every node: 3 VALU per node step against 3 VGPRs)
-#ifndef PTGS_PT_NODE64_PIN
-#define PTGS_PT_NODE64_PIN 1
-#endif
-// PTGS_PT_PK_SLAB: the near and the far plane of one axis and child share the multiplier and the addend, so the
-// six slab distances of a child are three two-element FMAs {near, far} (v_pk_fma_f32: the shared operands are
-// broadcast by op_sel, no pairing moves), and the four tf * 1.0000004f are two two-element multiplies. Each
-// element is the same single-rounding operation as the scalar form: tn, tf, the hit masks and the image do not
-// change. An explicit builtin, not a contracted multiply-add and not the SLP vectoriser (build.py). Only
-// box4_q: the float-plane box4 above is not touched (pairing its children needed moves and measured -1.4%).
-// Off: closest-hit node step 217 -> 203 instructions (145 -> 131 VALU), shadow node step 164 -> 151 (108 -> 94),
-// 12 v_pk_fma_f32 + 2 v_pk_mul_f32 per step and no v_mov added, and C3 at 64 spp 6 346 -> 6 034 Mrays/s (-4.9%;
-// with the multiplies left scalar, PTGS_PT_PK_SLAB_MUL=0: 6 082, -4.2%; tools/ab_pt.py, images identical). A packed
-// f32 operation takes longer to issue here than the two scalar ones it replaces (profiles/r10_summary.md), which
-// is also why pt_kernels.hip is built without the SLP vectoriser (build.py).
-#ifndef PTGS_PT_PK_SLAB
-#define PTGS_PT_PK_SLAB 0
-#endif
-#ifndef PTGS_PT_PK_SLAB_MUL  // (with PK_SLAB) 0: the four multiplies stay scalar
-#define PTGS_PT_PK_SLAB_MUL 1
-#endif
+// The slab FMAs stay scalar: a packed f32 operation takes longer to issue here than the two scalar ones it
+// replaces (tools/patches/pt_pk_slab_rejected.patch), which is also why pt_kernels.hip
+// is built without the SLP vectoriser (build.py).
+// node64_ray: the walk keeps o * inv in registers (the compiler otherwise recomputes the three products at every
+// node: 3 VALU per node step against 3 VGPRs)
 template <bool N64>
 __device__ __forceinline__ Ray node64_ray(const Ray& r) {
   Ray q = r;
-  if (N64 && PTGS_PT_NODE64_PIN) asm volatile("" : "+v"(q.oinv.x), "+v"(q.oinv.y), "+v"(q.oinv.z));
+  if (N64) asm volatile("" : "+v"(q.oinv.x), "+v"(q.oinv.y), "+v"(q.oinv.z));
   return q;
 }
 __device__ __forceinline__ float node64_q(uint32_t w, int j) { return (float)((w >> (8 * j)) & 0xffu); }
@@ -455,65 +397,18 @@ __device__ __forceinline__ void box4_q(const Ray& r, const DevScene& sc, int nod
   const float cx = __builtin_fmaf(__uint_as_float(a.x), r.inv.x, -r.oinv.x);
   const float cy = __builtin_fmaf(__uint_as_float(a.y), r.inv.y, -r.oinv.y);
   const float cz = __builtin_fmaf(__uint_as_float(a.z), r.inv.z, -r.oinv.z);
-#if PTGS_PT_NEARFAR
   const bool gx = (r.nx & 16u) != 0u, gy = (r.ny & 16u) != 0u, gz = (r.nz & 16u) != 0u;  // inv < 0: hi is near
-#else
-  const bool gx = r.inv.x < 0.0f, gy = r.inv.y < 0.0f, gz = r.inv.z < 0.0f;
-#endif
   const uint32_t nX = gx ? b.w : b.z, fX = gx ? b.z : b.w;
   const uint32_t nY = gy ? p.y : p.x, fY = gy ? p.x : p.y;
   const uint32_t nZ = gz ? p.w : p.z, fZ = gz ? p.z : p.w;
   const uint32_t CH[4] = {ch.x, ch.y, ch.z, ch.w};
-#if PTGS_PT_PK_SLAB
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  const f2 SX = {sx, sx}, SY = {sy, sy}, SZ = {sz, sz}, CX = {cx, cx}, CY = {cy, cy}, CZ = {cz, cz};
-  float TN[4], TF[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const f2 qx = {node64_q(nX, j), node64_q(fX, j)}, qy = {node64_q(nY, j), node64_q(fY, j)};
-    const f2 qz = {node64_q(nZ, j), node64_q(fZ, j)};
-    const f2 x = __builtin_elementwise_fma(qx, SX, CX);  // {near, far}
-    const f2 y = __builtin_elementwise_fma(qy, SY, CY);
-    const f2 z = __builtin_elementwise_fma(qz, SZ, CZ);
-    TN[j] = fmaxf(fmaxf(x.x, y.x), fmaxf(z.x, r.tmin));
-#if PTGS_PT_ASM_MIN
-    float tf;
-    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(tf) : "v"(x.y), "v"(y.y), "v"(z.y));
-    asm("v_min_f32 %0, %1, %2" : "=v"(tf) : "v"(tf), "v"(tcap));
-    TF[j] = tf;
-#else
-    TF[j] = fminf(fminf(x.y, y.y), fminf(z.y, tcap));
-#endif
-  }
-#if PTGS_PT_PK_SLAB_MUL
-  const f2 K = {1.0000004f, 1.0000004f};
-  const f2 f01 = (f2){TF[0], TF[1]} * K, f23 = (f2){TF[2], TF[3]} * K;
-  const float TFK[4] = {f01.x, f01.y, f23.x, f23.y};
-#else
-  const float TFK[4] = {TF[0] * 1.0000004f, TF[1] * 1.0000004f, TF[2] * 1.0000004f, TF[3] * 1.0000004f};
-#endif
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    unsigned long long hm = __builtin_amdgcn_ballot_w64(TN[j] <= TFK[j]);
-    if (j >= 2) hm &= __builtin_amdgcn_ballot_w64(CH[j] != 0u);
-    o.tn[j] = __builtin_amdgcn_inverse_ballot_w64(hm) ? TN[j] : __builtin_huge_valf();
-    o.c[j] = (int)CH[j];
-    o.hm[j] = hm;
-  }
-#else
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const float x0 = __builtin_fmaf(node64_q(nX, j), sx, cx), x1 = __builtin_fmaf(node64_q(fX, j), sx, cx);
     const float y0 = __builtin_fmaf(node64_q(nY, j), sy, cy), y1 = __builtin_fmaf(node64_q(fY, j), sy, cy);
     const float z0 = __builtin_fmaf(node64_q(nZ, j), sz, cz), z1 = __builtin_fmaf(node64_q(fZ, j), sz, cz);
     const float tn = fmaxf(fmaxf(x0, y0), fmaxf(z0, r.tmin));
-#if PTGS_PT_ASM_MIN
-    float tf;
-    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(tf) : "v"(x1), "v"(y1), "v"(z1));
-    asm("v_min_f32 %0, %1, %2" : "=v"(tf) : "v"(tf), "v"(tcap));
-#else
-    const float tf = fminf(fminf(x1, y1), fminf(z1, tcap));
-#endif
+    const float tf = far_min(x1, y1, z1, tcap);
     // (the two compares' lane masks combined on the scalar unit)
     unsigned long long hm = __builtin_amdgcn_ballot_w64(tn <= tf * 1.0000004f);
     if (j >= 2) hm &= __builtin_amdgcn_ballot_w64(CH[j] != 0u);
@@ -521,7 +416,6 @@ __device__ __forceinline__ void box4_q(const Ray& r, const DevScene& sc, int nod
     o.c[j] = (int)CH[j];
     o.hm[j] = hm;
   }
-#endif
 }
 template <bool N64>
 __device__ __forceinline__ void box4_sel(const Ray& r, const DevScene& sc, int node, float tcap, Box4& o) {
@@ -537,9 +431,9 @@ __device__ __forceinline__ void cswap4(Box4& b, int i, int j) {
 }
 // The next node of a closest-hit walk after a 4-wide node test: the nearest hit child, the other hit
 // children pushed farthest first; no hit child: pop().
-// (enter_box4_hit: the same for a lane with a hit child, for the walk that pops at a site of its own)
-template <typename Push>
-__device__ __forceinline__ int enter_box4_hit(Box4& b, Push push) {
+template <typename Push, typename Pop>
+__device__ __forceinline__ int enter_box4(Box4& b, Push push, Pop pop) {
+  if (!__builtin_amdgcn_inverse_ballot_w64(b.hm[0] | b.hm[1] | b.hm[2] | b.hm[3])) return pop();
   const unsigned long long h0 = b.hm[0], h1 = b.hm[1], h2 = b.hm[2], h3 = b.hm[3];
   cswap4(b, 0, 1); cswap4(b, 2, 3); cswap4(b, 0, 2); cswap4(b, 1, 3); cswap4(b, 1, 2);
   // (the sorted hits come first: at least 4 / 3 / 2 of the four children hit, as lane masks)
@@ -550,11 +444,6 @@ __device__ __forceinline__ int enter_box4_hit(Box4& b, Push push) {
   if (__builtin_amdgcn_inverse_ballot_w64(a01 | a23 | (o01 & o23))) push(b.c[1], b.tn[1]);
   return b.c[0];
 }
-template <typename Push, typename Pop>
-__device__ __forceinline__ int enter_box4(Box4& b, Push push, Pop pop) {
-  if (!__builtin_amdgcn_inverse_ballot_w64(b.hm[0] | b.hm[1] | b.hm[2] | b.hm[3])) return pop();
-  return enter_box4_hit(b, push);
-}
 
 // SS: the LDS stack's stride (work-items sharing it); OVF: overflow entries beyond the LDS part (0 for
 // a tree whose stack need fits the LDS part: the overflow's branches and scratch cost 3.4% on C3); LDS: the
@@ -562,7 +451,7 @@ __device__ __forceinline__ int enter_box4(Box4& b, Push push, Pop pop) {
 // N64: fetch the compact nodes (box4_q); their links are packed (stack_key.h): an interior index as it is,
 // a leaf with its count right above the first triangle's bits, so that the link takes the fewest bits the
 // tree needs (C3: 21, C5: 23) and the sign still tells a leaf.
-// CULL (with N64; PTGS_PT_STACK_CULL): a pushed entry keeps, in the bits the link leaves free, the floor of
+// CULL (with N64; the megakernel's walk): a pushed entry keeps, in the bits the link leaves free, the floor of
 // the child's entry distance tn from the box test that pushed it (one v_and_or_b32 per push). pop() drops
 // every entry whose bound is > h.t * 1.0000004f: the box test that pushed it, repeated with today's h.t,
 // would miss (tf <= h.t, and the bound is <= tn), so the node fetch, its four box tests and the leaf's
@@ -570,43 +459,15 @@ __device__ __forceinline__ int enter_box4(Box4& b, Push push, Pop pop) {
 // t == h.t with a lower gid is still found. Any candidate at t lies in its subtree's box, whose stored tn is
 // <= t, so no culled entry holds a candidate with t <= h.t: hits, ray counts and the image are
 // those of the walk that does not cull. A key of 0 bits (sc.stk_key_mask 0) bounds every entry by 0.0 and
-// never culls. trace_any has a constant cap and never culls. C3 at 64 spp, interleaved (tools/ab_pt.py):
-// 5 781 Mrays/s without, 6 048 with (closest-hit node steps 356.9 M -> 288.1 M wave iterations); a pop()
-// that tests the empty stack as a second loop exit instead of popping DONE as a never-culled word: 5 886.
-#ifndef PTGS_PT_STACK_CULL
-#define PTGS_PT_STACK_CULL 1
-#endif
-// PTGS_PT_ONE_POP: one pop site in the node step of trace_closest instead of two copies of the culling pop loop
-// (enter_box4's "no child hit" pop, and the pop after the entered leaf is parked). A lane needs a pop when no
-// child was hit, or when its nearest child is a leaf and it holds none.
-//   1: every lane visits the nodes and leaves it visited before, in the same order. A lane that pops a leaf
-//      while it holds none parks it and pops again: a second pass of the one pop loop (its condition: the word
-//      is culled, or it was parked), not a second site.
-//   2: the lane pops once. A leaf popped by a lane with no hit child leaves the node loop in `node`, where the
-//      code after the loop tests it as it tests a second leaf. The closest hit is a minimum over candidates, so
-//      the hits are the same; a lane no longer walks on past such a leaf, so the lane steps move.
-//   0: the two sites (shipped).
-// Both one-site forms are off. Closest-hit node step in the ISA 217 -> 193 (form 1) and 195 (form 2)
-// instructions, and C3 at 64 spp, interleaved with the SLP packing off (build.py): 6 529 Mrays/s with the two
-// sites, 6 508 with form 1, 6 529 with form 2; on top of PTGS_PT_ULOOP 6 548 -> 6 533 and 6 547. The second pop
-// site is an exec region of its own, entered only in a step in which a lane parks a leaf; how often a wave
-// skips it was not measured, and the time did not follow the static count. Form 2 visits C3's nodes in 296.5 M wave steps instead
-// of 288.1 M (lane steps -0.1%). C5's DEEP instantiation, whose pop carries the overflow's branches, gains from
-// form 2 (3 266 -> 3 339 Mrays/s), but no more than 0.5% beyond what PTGS_PT_ULOOP gives it (3 322).
-// PTGS_PT_ULOOP: the node loop's test `node >= 0 && node != DONE` as one unsigned compare. It rests on: a leaf
+// never culls. trace_any has a constant cap and never culls. An empty stack pops DONE as a never-culled word,
+// so pop()'s loop has one exit (figures: DESIGN.md §5, round 8).
+// The node step pops at two sites: enter_box4's "no child hit" pop, and the pop after the entered leaf is parked.
+// The second is an exec region of its own, entered only in a step in which a lane parks a leaf. The two forms
+// with one pop site measured no faster (tools/patches/pt_one_pop_rejected.patch).
+// The node loop's test `node >= 0 && node != DONE` is one unsigned compare. It rests on: a leaf
 // link has bit 31 set, so as unsigned it is above DONE (0x7fffffff, less the key's bits in the culling walk);
 // and DONE is above every interior index (bvh.cpp stack_layout sizes the link's bits for the node count, and
-// the key takes only what they leave). On: C3 6 529 -> 6 548 Mrays/s (+0.3%), C5's mesh 3 266 -> 3 322 (+1.7%).
-// In trace_any it leaves the shadow node step at 165 instructions.
-#ifndef PTGS_PT_ONE_POP
-#define PTGS_PT_ONE_POP 0
-#endif
-#ifndef PTGS_PT_ULOOP
-#define PTGS_PT_ULOOP 1
-#endif
-#ifndef PTGS_PT_ULOOP_ANY  // the same test in trace_any's single-exit walk
-#define PTGS_PT_ULOOP_ANY PTGS_PT_ULOOP
-#endif
+// the key takes only what they leave).
 template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF, bool N64 = false, bool CULL = false, int LDS = PTGS_STACK>
 __device__ __forceinline__ Hit trace_closest(const DevScene& sc, const Ray& r, uint32_t seed, int* stack,
                                              TraversalCounters& cnt) {
@@ -649,65 +510,22 @@ __device__ __forceinline__ Hit trace_closest(const DevScene& sc, const Ray& r, u
     } while (stack_bound(x, kmask) > cap);
     return (int)stack_link(x, kmask);
   };
-  // PTGS_PT_ONE_POP=1: pop(), and while the popped word is a leaf and the lane holds none, park it and pop again
-  auto pop_park = [&]() -> int {
-    const float cap = h.t * 1.0000004f;
-    int n;
-    bool again;
-    do {
-      uint32_t x = (uint32_t)DONE;
-      if (sp) {
-        --sp;
-        x = (uint32_t)((OVF == 0 || sp < LDS) ? stack[sp * SS] : ovf[sp - LDS]);
-      }
-      n = CULL ? (int)stack_link(x, kmask) : (int)x;
-      again = CULL && stack_bound(x, kmask) > cap;
-      if (!again && n < 0 && leaf == DONE) {
-        leaf = n;
-        again = true;
-      }
-    } while (again);
-    return n;
-  };
   // (a register-cached stack top that hides the LDS read behind the node fetch measured -0.8%)
   for (;;) {
-#if PTGS_PT_ULOOP
-    while ((uint32_t)node < (uint32_t)DONE) {
-#else
-    while (node >= 0 && node != DONE) {
-#endif
+    while ((uint32_t)node < (uint32_t)DONE) {  // (an interior node: see above)
       PT_LANE_TICK(cnt, PT_L_NODE);
       Box4 b;
       box4_sel<N64>(rq, sc, node, h.t, b);
       if (STATS) cnt.nodes += 4;
-#if PTGS_PT_ONE_POP
-      bool need = !__builtin_amdgcn_inverse_ballot_w64(b.hm[0] | b.hm[1] | b.hm[2] | b.hm[3]);
-      if (!need) {
-        node = enter_box4_hit(b, push);
-        if (node < 0 && leaf == DONE) {
-          leaf = node;
-          need = true;
-        }
-      }
-      if (need) node = PTGS_PT_ONE_POP == 1 ? pop_park() : pop();
-#else
       node = enter_box4(b, push, pop);
       if (node < 0 && leaf == DONE) {
         leaf = node;
         node = pop();
       }
-#endif
       // (every active lane holds a leaf or is done: the compares' lane mask against exec, no VGPR round trip)
-#if PTGS_PT_ONE_POP == 2
-      // (or holds in `node` a leaf it popped: it leaves the loop at the test above)
-      if ((__builtin_amdgcn_ballot_w64(leaf != DONE) | __builtin_amdgcn_ballot_w64((uint32_t)node >= (uint32_t)DONE)) ==
-          __builtin_amdgcn_read_exec())
-        break;
-#else
       if ((__builtin_amdgcn_ballot_w64(leaf != DONE) | __builtin_amdgcn_ballot_w64(node == DONE)) ==
           __builtin_amdgcn_read_exec())
         break;
-#endif
     }
     if (leaf != DONE) {
       PT_LANE_TICK(cnt, PT_L_LEAF);
@@ -722,66 +540,20 @@ __device__ __forceinline__ Hit trace_closest(const DevScene& sc, const Ray& r, u
   }
 }
 
-// PTGS_PT_ANY_SINGLE_EXIT: the any-hit (shadow) walk in trace_closest's shape. One `occluded` flag per lane, the
-// empty stack pops the DONE sentinel (0x7fffffff: no interior index reaches it, bvh.cpp stack_layout; a leaf
-// link is negative), and the walk returns at one place; no return or continue inside the node or the triangle
-// loop. The entered child is the first hit child in slot order (a select chain over the scalar hit masks
-// Box4::hm), child j is pushed when it and an earlier child are hit (mask expressions on the scalar unit, as
-// enter_box4's), no hit child pops. No sort: near-to-far order measured -9% for shadow rays. Any-hit is an OR
-// over the leaves the ray's boxes reach, so neither the push order nor the visiting order changes the result.
-// Every push is under the exec mask of the lanes whose mask bit is set: a lane that is done, or whose child
-// is missed, stores nothing, and the stack depth is that of the walk it replaces (one entered, the other hit
-// children pushed).
-// PTGS_PT_ANY_PARK (with SINGLE_EXIT): the postponed leaf of trace_closest. A lane that reaches a leaf parks it
-// and walks on until every lane in the loop holds a leaf or is done; one leaf routine, one call site. A lane
-// whose leaf occludes drops what its stack still holds (node = DONE). Off: the lanes of a wave already meet at
-// the leaf (the node loop ends when the last of them reaches one), so parking only lets a lane run ahead into
-// nodes that are wasted when its parked leaf occludes.
-// C3 at 64 spp, interleaved (tools/ab_pt.py; profiles/r09_summary.md): the walk before 6 076 Mrays/s, single
-// exit 6 357, single exit with the postponed leaf 6 275. Shadow node step in the ISA: 224 instructions (120
-// VALU, 96 SALU) -> 164 (108, 48); with the postponed leaf 178 (117, 53).
-#ifndef PTGS_PT_ANY_SINGLE_EXIT
-#define PTGS_PT_ANY_SINGLE_EXIT 1
-#endif
-#ifndef PTGS_PT_ANY_PARK
-#define PTGS_PT_ANY_PARK 0
-#endif
-// PTGS_PT_ANY_TRI_FOLD: the shadow leaf's triangle test without tri_isect's early returns (leaf_any below):
-// triangle step 117 instructions (72 VALU, 41 SALU) -> 106 (67, 35); 6 360 against 6 357 Mrays/s, a tie.
-// PTGS_PT_ANY_TRI_PREFETCH: leaf_closest's one-triangle-ahead fetch in the shadow leaf: 6 325, -0.5%; off.
-#ifndef PTGS_PT_ANY_TRI_FOLD
-#define PTGS_PT_ANY_TRI_FOLD 1
-#endif
-#ifndef PTGS_PT_ANY_TRI_PREFETCH
-#define PTGS_PT_ANY_TRI_PREFETCH 0
-#endif
 // One leaf of the any-hit walk: true when a triangle in [tmin, tmax] is hit and accepted. The loop ends at the
-// first such triangle (its one exit: the loop condition).
+// first such triangle (its one exit: the loop condition). The next triangle is not fetched ahead as in
+// leaf_closest: shadow leaves end at the first occluder (tools/patches/pt_any_tri_prefetch_rejected.patch).
 template <bool STATS, bool TEX, bool PK>
 __device__ __forceinline__ bool leaf_any(const DevScene& sc, const Ray& r, int leaf, uint32_t seed,
                                          TraversalCounters& cnt) {
   uint32_t start, count;
   leaf_range<PK>(sc, leaf, start, count);
   bool occ = false;
-#if PTGS_PT_ANY_TRI_PREFETCH
-  float4 na = sc.tris[3u * start], nb = sc.tris[3u * start + 1u], nc = sc.tris[3u * start + 2u];
-#endif
   for (uint32_t k = 0; k < count && !occ; ++k) {
     PT_LANE_TICK(cnt, PT_L_ANY_TRI);
-#if PTGS_PT_ANY_TRI_PREFETCH
-    float4 a = na, bb = nb, c = nc;  // (as leaf_closest: the next triangle in flight while this one is tested)
-    asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(bb.x), "+v"(bb.y), "+v"(bb.z), "+v"(bb.w),
-                      "+v"(c.x), "+v"(c.y), "+v"(c.z), "+v"(c.w));
-    if (k + 1 < count) {
-      const float4* tn = sc.tris + 3u * (start + k + 1u);
-      na = tn[0]; nb = tn[1]; nc = tn[2];
-    }
-#else
     const float4* tp = sc.tris + 3u * (start + k);
     float4 a = tp[0], bb = tp[1], c = tp[2];
-#endif
     if (STATS) cnt.tris++;
-#if PTGS_PT_ANY_TRI_FOLD
     // tri_isect's expressions with its early returns folded into one predicate: the same operations in the
     // same order give the same u, v, t wherever tri_isect returns true, and where it returns false early
     // (det == 0: inv_det is infinite) the first term is false. A wave of shadow rays almost never has every
@@ -796,11 +568,6 @@ __device__ __forceinline__ bool leaf_any(const DevScene& sc, const Ray& r, int l
     const float v = dot3(r.d, qvec) * inv_det;
     const float t = dot3(e2, qvec) * inv_det;
     bool hit = (det != 0.0f) & !(u < 0.0f) & !(u > 1.0f) & !(v < 0.0f) & !(u + v > 1.0f) & (t >= r.tmin) & (t <= r.tmax);
-#else
-    float t, u, v;
-    bool hit = tri_isect(r, mk3(a.x, a.y, a.z), mk3(bb.x, bb.y, bb.z), mk3(c.x, c.y, c.z), t, u, v);
-    hit = hit && t >= r.tmin && t <= r.tmax;
-#endif
     if (hit && sc.has_transparent && (sc.tri_flags[start + k] & 1u))
       hit = anyhit_accept<TEX>(sc, f2u(a.w), f2u(bb.w), u, v, seed, f2u(c.w));
     occ = hit;
@@ -808,6 +575,19 @@ __device__ __forceinline__ bool leaf_any(const DevScene& sc, const Ray& r, int l
   return occ;
 }
 
+// The any-hit (shadow) walk has trace_closest's shape. One `occluded` flag per lane, the
+// empty stack pops the DONE sentinel (0x7fffffff: no interior index reaches it, bvh.cpp stack_layout; a leaf
+// link is negative), and the walk returns at one place; no return or continue inside the node or the triangle
+// loop. The entered child is the first hit child in slot order (a select chain over the scalar hit masks
+// Box4::hm), child j is pushed when it and an earlier child are hit (mask expressions on the scalar unit, as
+// enter_box4's), no hit child pops. No sort: near-to-far order measured -9% for shadow rays. Any-hit is an OR
+// over the leaves the ray's boxes reach, so neither the push order nor the visiting order changes the result.
+// Every push is under the exec mask of the lanes whose mask bit is set: a lane that is done, or whose child
+// is missed, stores nothing, and the stack holds what a lane-by-lane walk would (one child entered, the other hit
+// children pushed).
+// No postponed leaf as in trace_closest: the lanes of a wave already meet at the leaf (the node loop ends when
+// the last of them reaches one), so parking only lets a lane run ahead into nodes that are wasted when its
+// parked leaf occludes (tools/patches/pt_any_park_rejected.patch). Figures: DESIGN.md §5, round 9.
 template <bool STATS, bool TEX, int SS = PTGS_BLOCK, int OVF = PTGS_STACK_OVF, bool N64 = false, int LDS = PTGS_STACK>  // (as trace_closest)
 __device__ __forceinline__ bool trace_any(const DevScene& sc, const Ray& r, uint32_t seed, int* stack,
                                           TraversalCounters& cnt) {
@@ -815,7 +595,6 @@ __device__ __forceinline__ bool trace_any(const DevScene& sc, const Ray& r, uint
   int sp = 0;
   int node = 0;
   int ovf[OVF > 0 ? OVF : 1];  // entries beyond the LDS part (private: scratch)
-#if PTGS_PT_ANY_SINGLE_EXIT
   const int DONE = 0x7fffffff;
   bool occluded = false;
   auto push = [&](int c) {
@@ -828,13 +607,8 @@ __device__ __forceinline__ bool trace_any(const DevScene& sc, const Ray& r, uint
     --sp;
     return (OVF == 0 || sp < LDS) ? stack[sp * SS] : ovf[sp - LDS];
   };
-  int leaf = DONE;  // (PARK: the postponed leaf)
   for (;;) {
-#if PTGS_PT_ULOOP_ANY
     while ((uint32_t)node < (uint32_t)DONE) {  // (as trace_closest)
-#else
-    while (node >= 0 && node != DONE) {
-#endif
       PT_LANE_TICK(cnt, PT_L_ANY_NODE);
       Box4 b;
       box4_sel<N64>(rq, sc, node, r.tmax, b);
@@ -852,91 +626,14 @@ __device__ __forceinline__ bool trace_any(const DevScene& sc, const Ray& r, uint
       } else {
         node = pop();
       }
-      if (PTGS_PT_ANY_PARK) {
-        if (node < 0 && leaf == DONE) {
-          leaf = node;
-          node = pop();
-        }
-        // (every active lane holds a leaf or is done: as trace_closest)
-        if ((__builtin_amdgcn_ballot_w64(leaf != DONE) | __builtin_amdgcn_ballot_w64(node == DONE)) ==
-            __builtin_amdgcn_read_exec())
-          break;
-      }
     }
-    if (PTGS_PT_ANY_PARK) {
-      if (leaf != DONE) {
-        occluded = leaf_any<STATS, TEX, N64>(sc, r, leaf, seed, cnt);
-        leaf = DONE;
-        if (occluded) node = DONE;
-      }
-      // (a second leaf reached while one was parked: it is the next round's)
-      if (node < 0) {
-        leaf = node;
-        node = pop();
-      }
-      if (node == DONE && leaf == DONE) return occluded;
-    } else {
-      if (node < 0) {
-        occluded = leaf_any<STATS, TEX, N64>(sc, r, node, seed, cnt);
-        node = pop();
-        if (occluded) node = DONE;
-      }
-      if (node == DONE) return occluded;
+    if (node < 0) {
+      occluded = leaf_any<STATS, TEX, N64>(sc, r, node, seed, cnt);
+      node = pop();
+      if (occluded) node = DONE;
     }
+    if (node == DONE) return occluded;
   }
-#else
-  auto pop_nz = [&]() -> int {  // sp > 0
-    --sp;
-    return (OVF == 0 || sp < LDS) ? stack[sp * SS] : ovf[sp - LDS];
-  };
-  while (true) {
-    while (node >= 0) {
-      PT_LANE_TICK(cnt, PT_L_ANY_NODE);
-      Box4 b;
-      box4_sel<N64>(rq, sc, node, r.tmax, b);
-      if (STATS) cnt.nodes += 4;
-      // order is irrelevant for an any-hit query: enter the first hit child, push the others (the
-      // closest-hit near-to-far order measured -9% for the shadow rays)
-      int next = -0x7fffffff - 1;
-      bool have = false;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (b.tn[j] != __builtin_huge_valf()) {
-          if (!have) {
-            next = b.c[j];
-            have = true;
-          } else {
-            if (OVF == 0 || sp < LDS) stack[sp * SS] = b.c[j];
-            else ovf[sp - LDS] = b.c[j];
-            ++sp;
-          }
-        }
-      if (!have) {
-        if (sp == 0) return false;
-        node = pop_nz();
-        continue;
-      }
-      node = next;
-    }
-    uint32_t start, count;
-    leaf_range<N64>(sc, node, start, count);  // (the compact nodes' links are packed)
-    for (uint32_t k = 0; k < count; ++k) {
-      PT_LANE_TICK(cnt, PT_L_ANY_TRI);
-      const float4* tp = sc.tris + 3u * (start + k);
-      float4 a = tp[0], bb = tp[1], c = tp[2];
-      if (STATS) cnt.tris++;
-      float t, u, v;
-      if (!tri_isect(r, mk3(a.x, a.y, a.z), mk3(bb.x, bb.y, bb.z), mk3(c.x, c.y, c.z), t, u, v)) continue;
-      if (!(t >= r.tmin && t <= r.tmax)) continue;
-      if (sc.has_transparent && (sc.tri_flags[start + k] & 1u)) {
-        if (!anyhit_accept<TEX>(sc, f2u(a.w), f2u(bb.w), u, v, seed, f2u(c.w))) continue;
-      }
-      return true;
-    }
-    if (sp == 0) return false;
-    node = pop_nz();
-  }
-#endif
 }
 
 __device__ __forceinline__ v4 matvec(const float* m, v4 v) {

@@ -7,20 +7,18 @@
 //   pt_depth_kernel  : primary-hit view depth per pixel (pixel-centre ray of raygen_camera.rgen:25-41)
 //                      for the hybrid splat-over-path-trace composite.
 //
-// Launch geometry: 256-thread workgroups = 4 waves, each wave an 8x8 pixel tile (primary-ray
-// coherence for the BVH walk), workgroup = 16x16 pixels; 1080p -> 8,160 workgroups (>> 256 CUs).
+// Launch geometry. pt_camera_kernel: one-wave workgroups (PTGS_PT_WG), each an 8x8 pixel tile (primary-ray
+// coherence for the BVH walk), or 8x4 / 8x2 with two / four lanes per pixel; 1080p -> 32,400 workgroups or more
+// (>> 256 CUs); a finished tile frees its slot at once. The torus and depth kernels:
+// 256-thread workgroups.
 #include <hip/hip_runtime.h>
 
 #include "pt_shade.h"
 #include "pt_launch.h"
-#include "xcd.h"
 
-#ifndef PTGS_PT_XCD_REMAP
-#define PTGS_PT_XCD_REMAP 0
-#endif
-#ifndef PTGS_PT_WG
-#define PTGS_PT_WG 64  // pt_camera_kernel workgroup: one wave per 8x8 pixel tile (256: four tiles per workgroup)
-#endif
+// pt_camera_kernel's workgroup: one wave per pixel tile. (256-thread workgroups of four tiles, and an XCD-aware
+// block -> tile remap on them, measured slower: DESIGN.md §5, rounds 2 and 3; tools/patches/pt_xcd_remap_wg256_rejected.patch)
+#define PTGS_PT_WG 64
 #ifndef PTGS_PT_PAIR
 #define PTGS_PT_PAIR 1  // one-wave workgroups: two lanes per pixel (even / odd samples) when spp >= 2
 #endif
@@ -91,7 +89,7 @@ __device__ unsigned long long g_pt_stamps[PT_STAMP_WG * 2];
 // lanes per pixel of the one-wave tiles (log2): up to PTGS_PT_LPP (1, 2 or 4) when there are that many
 // samples to share
 __host__ __device__ __forceinline__ uint32_t pt_lanes_log2(uint32_t spp) {
-  if (PTGS_PT_WG != 64 || !PTGS_PT_PAIR) return 0u;
+  if (!PTGS_PT_PAIR) return 0u;
   return (PTGS_PT_LPP >= 4 && spp >= 4u) ? 2u : (PTGS_PT_LPP >= 2 && spp >= 2u) ? 1u : 0u;
 }
 
@@ -103,17 +101,11 @@ __global__ __launch_bounds__(PTGS_PT_WG, DEEP ? PTGS_PT_DEEP_MIN_WAVES : PTGS_PT
                                                         uint32_t mode, unsigned long long* counters,
                                                         const uint32_t* __restrict__ order, uint32_t* __restrict__ cost) {
   const uint32_t lid = threadIdx.x;
-  const uint32_t wave = lid >> 6, lane = lid & 63u;
+  const uint32_t lane = lid & 63u;
 #ifdef PT_STAMP
   const uint32_t swg = blockIdx.y * gridDim.x + blockIdx.x;
   if (lid == 0 && swg < PT_STAMP_WG) g_pt_stamps[2 * swg] = __builtin_amdgcn_s_memrealtime();
 #endif
-#if PTGS_PT_XCD_REMAP
-  static_assert(PTGS_PT_WG == 256, "the XCD remap maps 16x16 tiles");
-  // XCD-aware: the workgroups of one XCD trace one horizontal strip of 16x16 tiles (shared L2 nodes)
-  const uint32_t tl = xcd_tile(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
-  const uint32_t bx = tl % gridDim.x, by = tl / gridDim.x;
-#else
   // tile schedule (PtSched): workgroup b renders tile order[b], the tiles that took longest in the
   // previous launch first, so the launch ends on short tiles; each tile's time is recorded for the
   // next launch. Any order gives the same image.
@@ -124,8 +116,6 @@ __global__ __launch_bounds__(PTGS_PT_WG, DEEP ? PTGS_PT_DEEP_MIN_WAVES : PTGS_PT
     bx = tl - by * gridDim.x;
   }
   const unsigned long long t_start = cost ? __builtin_amdgcn_s_memrealtime() : 0ull;
-#endif
-#if PTGS_PT_WG == 64
   // One wave per workgroup. With spp >= 2 (pair) it shades an 8x4 tile with two lanes per pixel: lane
   // l < 32 traces the even samples, l + 32 the odd ones, and after each pair the even lane folds both
   // results into the pixel's running mean in sample order (the same operations, in the same order,
@@ -138,13 +128,6 @@ __global__ __launch_bounds__(PTGS_PT_WG, DEEP ? PTGS_PT_DEEP_MIN_WAVES : PTGS_PT
   const uint32_t pl = lane & (pw - 1u);                    // its pixel in the 8 x (8 / lpp) tile
   const uint32_t x = bx * 8u + (pl & 7u);
   const uint32_t y = row0 + by * (8u >> llpp) + (pl >> 3);
-#else
-  const bool pair = false;
-  const uint32_t lpp = 1u, pw = 64u;
-  const uint32_t half = 0;
-  const uint32_t x = bx * 16u + (wave & 1u) * 8u + (lane & 7u);
-  const uint32_t y = row0 + by * 16u + (wave >> 1) * 8u + (lane >> 3);
-#endif
   const bool active = (x < W) && (y < row1);
 
   constexpr int kLds = pt_lds_stack(DEEP);
@@ -200,14 +183,13 @@ __global__ __launch_bounds__(PTGS_PT_WG, DEEP ? PTGS_PT_DEEP_MIN_WAVES : PTGS_PT
         p.depth = depth;
         Ray ray = make_ray(ro, rd, 0.001f, 10000.0f);
         ext_rays++;
-        Hit h = trace_closest<STATS, TEX, PTGS_PT_WG, kOvf, PTGS_PT_NODE64 != 0,
-                              PTGS_PT_NODE64 != 0 && PTGS_PT_STACK_CULL != 0, kLds>(sc, ray, p.seed, c.stack, tc);
+        Hit h = trace_closest<STATS, TEX, PTGS_PT_WG, kOvf, true, true, kLds>(sc, ray, p.seed, c.stack, tc);
         if (STATS && h.gid != 0xffffffffu) tc.hits++;
         ShadowQuery q;
         q.flags = 0;
         if (h.gid == 0xffffffffu) miss<false>(cp, p);
         else closest_hit<false, TEX>(c, p, ray, h, q);
-        resolve_shadow<STATS, TEX, PTGS_PT_WG, kOvf, PTGS_PT_NODE64 != 0, kLds>(c, p.color, p.seed, q, tc);  // NEE visibility after shading
+        resolve_shadow<STATS, TEX, PTGS_PT_WG, kOvf, true, kLds>(c, p.color, p.seed, q, tc);  // NEE visibility after shading
         acc = acc + p.color * thr;
         acc = vmin(acc, 5.0f);
         if (p.hit_flag < 0.0f) break;
@@ -249,12 +231,10 @@ __global__ __launch_bounds__(PTGS_PT_WG, DEEP ? PTGS_PT_DEEP_MIN_WAVES : PTGS_PT
   }
   flush_counters(counters, ext_rays, c.shadow_rays, samples, tc, STATS);
   PT_LANES_FLUSH(tc);
-#if !PTGS_PT_XCD_REMAP
   if (cost) {
     __syncthreads();  // (every wave of the tile is done)
     if (lid == 0) cost[by * gridDim.x + bx] = (uint32_t)min(__builtin_amdgcn_s_memrealtime() - t_start, 0xFFFFFFFFull);
   }
-#endif
 #ifdef PT_STAMP
   __syncthreads();
   if (lid == 0 && swg < PT_STAMP_WG) g_pt_stamps[2 * swg + 1] = __builtin_amdgcn_s_memrealtime();
@@ -461,14 +441,13 @@ hipError_t launch_pt_camera(const DevScene& sc, const CamParams& cp, float* accu
                             uint32_t mode, unsigned long long* counters, bool stats, PtSched* ps,
                             hipStream_t stream) {
   if (row1 <= row0 || spp == 0) return hipSuccess;
-  // tiles: 16x16 (256-thread workgroups), 8x8 (one wave), 8x4 (one wave, two lanes per pixel: spp >= 2)
-  const uint32_t tx = PTGS_PT_WG == 64 ? 8u : 16u;
-  const uint32_t ty = PTGS_PT_WG == 64 ? 8u >> pt_lanes_log2(spp) : 16u;
+  // tiles: 8x8 (one wave), 8x4 (one wave, two lanes per pixel: spp >= 2)
+  const uint32_t tx = 8u;
+  const uint32_t ty = 8u >> pt_lanes_log2(spp);
   dim3 grid((W + tx - 1u) / tx, (row1 - row0 + ty - 1u) / ty);
   dim3 block(PTGS_PT_WG);
   const uint32_t *order = nullptr;
   uint32_t* cost = nullptr;
-#if !PTGS_PT_XCD_REMAP
   // heavy tiles first once a launch of this grid has recorded its tile times; launches of fewer than
   // PTGS_PT_SCHED_MIN pixel-samples skip it (C1's 65k: the order kernel's launch would cost more than
   // the tail it saves)
@@ -502,7 +481,6 @@ hipError_t launch_pt_camera(const DevScene& sc, const CamParams& cp, float* accu
     ps->gy = grid.y;
     cost = ps->cost;
   }
-#endif
   // (STATS, TEX, DEEP) instantiations: TEX only for scenes whose materials reference textures, DEEP only
   // when the walked copy's need reaches the megakernel's LDS stack (pt_deep_stack, not the canonical deep_stack)
   auto k = pt_camera_instantiation(stats, sc.uses_textures != 0, sc.pt_deep_stack != 0);

@@ -1,5 +1,5 @@
 // anyhit_walk_check — stand-alone host check of the path tracer's any-hit (shadow) walk
-// (pt_device.h trace_any / leaf_any: PTGS_PT_ANY_SINGLE_EXIT, PTGS_PT_ANY_PARK).
+// (pt_device.h trace_any / leaf_any; the postponed leaf: tools/patches/pt_any_park_rejected.patch).
 //
 //   anyhit_walk_check <tris.bin> <leaf> <fan> <depth> <waves>
 //
@@ -9,9 +9,11 @@
 // together and the loop ends when the last of them leaves, as the hardware's exec mask does it. The float
 // expressions are the kernel's (box4_q, tri_isect and leaf_any's folded form; -ffp-contract=off, explicit
 // fmaf). Three walks are modelled:
-//   old   the walk with two returns, a continue and the per-lane `have` chain (PTGS_PT_ANY_SINGLE_EXIT=0);
-//   se    single exit, the entered child and the pushes derived from the four children's wave hit masks;
-//   park  se with the postponed leaf.
+//   old   the walk with two returns, a continue and the per-lane `have` chain (the kernel's before the single
+//         exit: DESIGN.md §5, round 9);
+//   se    single exit, the entered child and the pushes derived from the four children's wave hit masks (the
+//         walk that ships);
+//   park  se with the postponed leaf (the patch).
 // Every fifth triangle is flagged non-opaque; a flagged triangle is accepted by a fixed hash of (gid, seed).
 // Rays, all seeded, four kinds in turn: a segment between two points of the scene bounds (tmax = its length
 // - 0.005, as shadow_towards); a general direction; one axis-parallel component (+0 / -0); an origin outside

@@ -1,5 +1,5 @@
 // closest_walk_check — stand-alone host check of the node step of the path tracer's closest-hit walk
-// (pt_device.h trace_closest<.., N64, CULL>: PTGS_PT_ONE_POP, PTGS_PT_ULOOP).
+// (pt_device.h trace_closest<.., N64, CULL>, and the one-pop-site forms of tools/patches/pt_one_pop_rejected.patch).
 //
 //   closest_walk_check <tris.bin> <leaf> <fan> <depth> <waves>
 //
@@ -10,13 +10,14 @@
 // expressions are the kernel's (box4_q, tri_isect and leaf_closest's tests; -ffp-contract=off, explicit fmaf);
 // the stack holds the packed words (stack_key.h) and pop drops every word whose bound is above the hit distance
 // of that moment. Three walks are modelled:
-//   old  two pop sites in the node step (PTGS_PT_ONE_POP=0): the "no child hit" pop of enter_box4, and the pop
+//   old  two pop sites in the node step (the walk that ships): the "no child hit" pop of enter_box4, and the pop
 //        after the entered leaf is parked;
-//   b1   one site (PTGS_PT_ONE_POP=1): a lane that pops a leaf while it holds none parks it and pops again,
+//   b1   one site (the patch's form 1): a lane that pops a leaf while it holds none parks it and pops again,
 //        a second pass of the one pop loop;
-//   b2   one site, one pop (PTGS_PT_ONE_POP=2): a leaf popped by a lane with no hit child leaves the node loop
+//   b2   one site, one pop (the patch's form 2): a leaf popped by a lane with no hit child leaves the node loop
 //        in `node`.
-// The node loop's test is the unsigned compare of PTGS_PT_ULOOP in b1 and b2 and the two signed compares in old.
+// The node loop's test is the kernel's one unsigned compare in b1 and b2 and the two signed compares it replaced
+// in old.
 // Rays, all seeded, four kinds in turn: two of a general direction from a point of the scene bounds, one with an
 // axis-parallel component (+0 / -0), one with its origin outside the bounds; tmax 1e4. Each wave has a random
 // subset of 1 to 64 active lanes, so the break ballot sees inactive lanes.
@@ -160,7 +161,7 @@ static uint32_t pop(const Tree& tr, Lane& l, Stats& st) {
   }
   return stack_link(x, km);
 }
-// PTGS_PT_ONE_POP=1: the one loop, whose condition is "culled, or parked"
+// form b1: the one loop, whose condition is "culled, or parked"
 static uint32_t pop_park(const Tree& tr, Lane& l, Stats& st) {
   const float cap = l.h.t * 1.0000004f;
   const uint32_t km = tr.lay.key_mask;
@@ -225,7 +226,7 @@ static void walk(const Tree& tr, Lane* L, int variant, Stats& st) {
         }
         Lane& l = L[i];
         bool need = !(anyc & bit);
-        if (!need) {  // enter_box4_hit: sorted, farthest pushed first
+        if (!need) {  // enter_box4 with a hit child: sorted, farthest pushed first
           auto cswap = [&](int a, int b) {
             if (tn[i][b] < tn[i][a]) { std::swap(tn[i][a], tn[i][b]); std::swap(c[i][a], c[i][b]); }
           };

@@ -205,7 +205,7 @@ static void walk_closest(const Tree& tr, const Mesh& m, Lane* L, Stats& st) {
         uint32_t c[4];
         box4(tr, l.r, l.node, l.h.t, hit, tn, c);
         const bool need = !(hit[0] || hit[1] || hit[2] || hit[3]);
-        if (!need) {  // enter_box4_hit: sorted, farthest pushed first
+        if (!need) {  // enter_box4 with a hit child: sorted, farthest pushed first
           auto cswap = [&](int a, int b) {
             if (tn[b] < tn[a]) { std::swap(tn[a], tn[b]); std::swap(c[a], c[b]); }
           };

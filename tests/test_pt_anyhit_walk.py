@@ -1,6 +1,6 @@
-"""The path tracer's any-hit (shadow) walk (pt_device.h trace_any / leaf_any: PTGS_PT_ANY_SINGLE_EXIT,
-PTGS_PT_ANY_PARK): single exit, the entered child and the pushes from the children's wave hit masks, one
-postponed leaf.
+"""The path tracer's any-hit (shadow) walk (pt_device.h trace_any / leaf_any): single exit, the entered child and
+the pushes from the children's wave hit masks; and the same with one postponed leaf
+(tools/patches/pt_any_park_rejected.patch).
 
 CPU part: tests/native/anyhit_walk_check.cpp, a stand-alone program (its own main, host code only: bvh.cpp and
 stack_key.h), built here with g++ -fsanitize=address,undefined and run directly. It models a wave of 64 lanes

@@ -1,21 +1,22 @@
-"""The node step of the path tracer's closest-hit walk (pt_device.h trace_closest: PTGS_PT_ONE_POP, one pop site
-instead of two; PTGS_PT_ULOOP, the node loop's test as one unsigned compare; PTGS_PT_PK_SLAB, the slab distances
-as two-element FMAs in box4_q).
+"""The node step of the path tracer's closest-hit walk (pt_device.h trace_closest: the two-site walk that ships, with
+the node loop's test as one unsigned compare; forms b1 and b2 with one pop site instead of two:
+tools/patches/pt_one_pop_rejected.patch; the slab distances as two-element FMAs in box4_q:
+tools/patches/pt_pk_slab_rejected.patch).
 
 CPU part: tests/native/closest_walk_check.cpp, a stand-alone program (its own main, host code only: bvh.cpp, bvh.h
 and stack_key.h), built here with g++ -fsanitize=address,undefined and run directly. It models a wave of 64 lanes
 in lockstep, with the packed stack words and the cull at pop, for the walk with two pop sites, for the one-site walk
-that parks a popped leaf and pops again (ONE_POP=1) and for the one-site walk that pops once (ONE_POP=2), on seeded
+that parks a popped leaf and pops again (form b1) and for the one-site walk that pops once (form b2), on seeded
 rays (general directions, one axis-parallel component, origins outside the bounds) in waves of 1 to 64 active
 lanes. The condition is zero violations: every walk returns the brute-force closest (t, gid) on every ray, no stack
-write at or above the tree's stack need, no write by a lane outside the node loop, and ONE_POP=1's per-lane
+write at or above the tree's stack need, no write by a lane outside the node loop, and form b1's per-lane
 sequence of visited nodes and leaves equals the two-site walk's. The program prints the modelled wave and lane node
 steps of the three walks (run pytest -s to see them).
 
 GPU part: the megakernel against the CPU oracle (which walks its own tree): images bit for bit (np.array_equal),
-extension and shadow ray counts equal. It runs the library as built: whichever of the three switches the build has
-on (the shipped build: the unsigned loop test in both walks; the one-site forms and the packed FMAs measured no
-gain and are off, profiles/r10_summary.md, where their images on the C3 frame are compared bit for bit with the
+extension and shadow ray counts equal. It runs the library as built (the unsigned loop test in both walks; a
+library built with one of the two patches runs that form: the one-site forms and the packed FMAs measured no
+gain, profiles/r10_summary.md, where their images on the C3 frame are compared bit for bit with the
 two-site walk's). A slab distance that rounded differently, or a lane that left the node loop on the wrong word,
 would move the visited boxes or lose a leaf; the image must not notice, the ray counts neither. The DEEP
 instantiation (stack need >= 39, entries in the private overflow) needs a tree of C5's size; no test scene builds

@@ -1,28 +1,19 @@
 #!/usr/bin/env python3
-"""A/B timing of path-tracer library variants (libptgs_<variant>.so built with extra -D flags) on the
+"""A/B timing of path-tracer library variants (libptgs_<variant>.so) on the
 C3 workload, interleaved rounds in ONE process (cdna_hip_programming.md §5.4 rule 24).
 
   python tools/ab_pt.py base w4 ...     (variant "base" = libptgs.so)
 
-e.g. the walk without the cull at pop: build.build(defines=("PTGS_PT_STACK_CULL=0",), variant="nocull"), then
-`tools/ab_pt.py nocull base`. The any-hit (shadow) walk's three forms in one process:
-build.build(defines=("PTGS_PT_ANY_SINGLE_EXIT=0",), variant="anyold") (the walk with two returns and the per-lane
-`have` chain), build.build(defines=("PTGS_PT_ANY_PARK=1",), variant="anypark") (single exit, pushes from the
-scalar hit masks, and the postponed leaf), then `tools/ab_pt.py anyold base anypark` (base: single exit without the
-postponed leaf). The shadow leaf's switches likewise: PTGS_PT_ANY_TRI_FOLD=0, PTGS_PT_ANY_TRI_PREFETCH=1.
-
-The node step's switches (profiles/r10_summary.md), one row each, every one with all three defines spelled out so
-that a row does not move when a default does:
-  variant   PTGS_PT_PK_SLAB  PTGS_PT_ONE_POP  PTGS_PT_ULOOP
-  par       0                0                0              the step before
-  a         1                0                0              packed slab FMAs (afma: and PTGS_PT_PK_SLAB_MUL=0)
-  ab1, ab2  1                1, 2             0              + one pop site, parking (1) or popping once (2)
-  b1, b2    0                1, 2             0              one pop site without the packed FMAs
-  c         0                0                1              the unsigned loop test alone (the default build)
-  b1c, b2c  0                1, 2             1
-`tools/ab_pt.py par a ab1 ab2 b1 b2 c b1c b2c`; the C5 mesh and the viewer rows for the kept combination:
-`AB_SCENE=c5 tools/ab_pt.py par base`, `AB_SPP=1 AB_CALLS=64 tools/ab_pt.py par base`. A variant built with other
-compiler flags (round 10's rows with and without the SLP vectoriser) sets build.EXTRA before build.build.
+A variant is a library built from a copy of the tree. A tunable number is a define:
+build.build(defines=("PTGS_PT_STACK=32",), variant="s32") or build.build(defines=("PTGS_PT_MIN_WAVES=4",),
+variant="w4"), then `tools/ab_pt.py base s32 w4`. A measured and rejected form of the traversal code is a patch in
+tools/patches/ (pt_pk_slab, pt_one_pop, pt_any_park, pt_any_tri_prefetch, pt_xcd_remap_wg256; figures in DESIGN.md
+§5): copy the tree, `git apply tools/patches/<file>` in the copy, and from the copy's package
+build.build(variant="pkslab") (each patch brings its switch, on by default, and a comment with the switch's values:
+-D<switch>=0 is the shipped form again); move libptgs_pkslab.so beside this tree's libptgs.so and run
+`tools/ab_pt.py base pkslab`. The C5 mesh and the viewer rows: `AB_SCENE=c5 tools/ab_pt.py base pkslab`,
+`AB_SPP=1 AB_CALLS=64 tools/ab_pt.py base pkslab`. A variant built with other compiler flags (round 10's rows with
+and without the SLP vectoriser) sets build.EXTRA before build.build.
 
 AB_SCENE=c5 times C5's mesh instead (the 1M-triangle atrium at 3840x2160, whose tree launches the DEEP
 kernels and whose nodes exceed an XCD's L2); AB_SPP, AB_ROUNDS, AB_CALLS as before. Each variant's image is

@@ -31,7 +31,7 @@ def main():
         torch.cuda.synchronize()
     dll = C.CDLL(lib)
     dll.ptgs_debug_pt_stamps.argtypes = [C.c_void_p, C.c_uint]
-    T = int(os.environ.get("PT_TILE", "8"))  # the workgroup tile edge (PTGS_PT_WG 64: 8, 256: 16)
+    T = int(os.environ.get("PT_TILE", "8"))  # the workgroup tile edge (16: the 256-thread workgroups of tools/patches/pt_xcd_remap_wg256_rejected.patch)
     TY = int(os.environ.get("PT_TILE_Y", "4" if T == 8 else str(T)))  # (8x4 tiles: two lanes per pixel)
     nwg = ((W + T - 1) // T) * ((H + TY - 1) // TY)
     st = np.zeros(2 * nwg, np.uint64)
